@@ -11,8 +11,11 @@ N > 1 (torch.distributed.run, one rank per GPU): every rank owns its own column 
 (weak scaling, no data-path collective - the reference's ranks do not communicate either, gt_mpi_gather.cc:322-366);
 value = records of all ranks / max-over-ranks time.
 
-Also on the JSON line: "roofline" for the dominant kernel (k_assemble_write, the HBM-bound gather-copy of entry texts into pages) and "cpu_baseline"
-(the CPU oracle = port of the reference algorithm, single thread, on a bounded sample of the same workload).
+Also on the JSON line: "roofline" for the dominant kernel (k_assemble_write, the HBM-bound gather-copy of entry texts into pages).
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: "roofline.alone"
+(the page kernel with one window in flight), the query-stream legs, the c3-shape leg and "cpu_baseline" (the CPU oracle = port of
+the reference algorithm, single thread, on a bounded sample of the same workload); each can still be left out with its --no-* option.
+--dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -63,7 +66,16 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="rank set-up, partition arithmetic and the cross-rank reduction only, no device work and no number: "
                          "lets the CPU suite check the N-rank launch (the line says \"dry_run\": true and carries value null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also the legs that take runs of their own: roofline.alone, the query-stream legs, the c3-shape leg "
+                         "and the CPU baseline (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32 / float64, < 64 MB; rank 0's partition)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.stream_input or args.c3_full):
+        ap.error("--dump-outputs covers the resident-array path (not --stream-input / --c3-full)")
     if args.c3_full:
         args.samples, args.interval_bp, args.window_bp, args.stream_input, args.base = 10000, 249_250_621, 50_000, True, 0   # (contig 1 of the vid: columns 0 .. 249 250 620)
 
@@ -114,7 +126,7 @@ def main():
     col = B
     while col < B + need_bp:
         col = min(B + need_bp, col + 1_000_000)
-        ptr, nbytes, nc = gen.next_chunk(col)
+        ptr, nbytes, nc = gen.next_chunk(col, nthreads=host_threads())
         eng.stage_cells_append(ptr, nbytes)
         ncells += nc
     eng.stage_cells_end()
@@ -168,11 +180,13 @@ def main():
         wk_launches += st.write_launches
     barrier()
     dt = time.time() - t1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, windows[total_steps - 1], st, arena)      # (st: the last timed step's statistics)
     # With several windows in flight a launch of the page kernel shares the device with the other lanes' kernels: its duration (what
     # `roofline` is computed from, as everywhere) says how long it was resident, not how fast it can go.  A short pass of the same
     # windows one at a time, OUTSIDE the timed region, measures the kernel on its own; it goes into roofline["alone"].
     alone = None
-    if lanes > 1 and not args.no_alone_pass:
+    if lanes > 1 and args.full and not args.no_alone_pass:
         a_ms = a_n = 0.0
         for i in range(args.warmup, min(total_steps, args.warmup + 3)):
             _, st1 = eng.run_interval(windows[i][0], windows[i][1], arena_bytes=arena, fetch=False)
@@ -233,7 +247,7 @@ def main():
             "untimed_lane_preparation_steps": (lanes if args.warmup < lanes else 0) if lanes > 1 else 0,
             "lanes_note": ("%d windows in flight at a time (gdbamd_engine_run_intervals: lane pipelines over one staged fragment); phase_ms and "
                            "roofline.avg_launch_ms are device times on each lane's own stream and overlap, so they add up to more than ms_per_step; "
-                           "roofline.alone is the same kernel measured with one window at a time, outside the timed region" % lanes) if lanes > 1 else None,
+                           "roofline.alone (--full) is the same kernel measured with one window at a time, outside the timed region" % lanes) if lanes > 1 else None,
             "whole_path_frac_of_hbm_peak": (bo_all + bi_all) / dt / 1e9 / HBM_PEAK_GBS / max(1, world),
             "stage_seconds_untimed": t_stage,
             "roofline": {"bound": "hbm", "kernel": "k_bcf_write" if args.bcf else "k_assemble_write", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -245,7 +259,7 @@ def main():
                                         "what": "%s with one window in flight (3 steps after the timed region)" % ("k_bcf_write" if args.bcf else "k_assemble_write")}
         if concat is not None:
             out["concat"] = concat
-        if not args.no_stream and world == 1 and not args.bcf:         # the boundary GATK drives: header + body through gdb_mi355_read
+        if args.full and not args.no_stream and world == 1 and not args.bcf:         # the boundary GATK drives: header + body through gdb_mi355_read
             eng.close()                                                 # (the timed engine's HBM - fragment, the lanes' arenas and tables - is given back first)
             # The same stream twice, the second one reported: the first stream of a process pays one-off costs - its pinned ring and, above all,
             # the first ~100 GB of device allocations after the timed engine gave ~180 GB back (3.3 - 3.4 s in front of the first byte on two of
@@ -256,8 +270,8 @@ def main():
             out["stream_end_to_end_bgzf"] = stream_end_to_end(N, B, min(W, Lbp), tmp, expect_body_bytes=None, output_format="z")
             # BCF2, what GATK4's GenomicsDBFeatureReader decodes: uncompressed ("bu", the JNI's is_bcf stream) and as BGZF blocks ("b")
             out["stream_end_to_end_bcf"] = {fmt: stream_end_to_end(N, B, min(W, Lbp), tmp, expect_body_bytes=None, output_format=fmt) for fmt in ("bu", "b")}
-        if not args.no_c3 and world == 1 and not args.bcf:
-            # BASELINE configs[2] shape in the default line: 10 000 samples, the array does NOT fit next to the working buffers and
+        if args.full and not args.no_c3 and world == 1 and not args.bcf:
+            # BASELINE configs[2] shape in the --full line: 10 000 samples, the array does NOT fit next to the working buffers and
             # passes through HBM in column windows with carry-over; the input path (host memory -> HBM) is inside the timed region
             import copy
             try:
@@ -267,12 +281,19 @@ def main():
             a3 = copy.copy(args)
             a3.samples, a3.interval_bp, a3.window_bp, a3.arena_mb = 10000, args.c3_bp, 50_000, 49152
             out["c3_streamed"] = run_streamed(a3, 0, 1, device_index, backend, source="memory", emit=False)
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(N, args.cpu_sample_bp, tmp)
     if out is not None:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def host_threads():
+    """threads for the synthetic generator: the CPUs this process may use (OMP_NUM_THREADS when set, else its CPU affinity), at most 48.
+    The generator's cells do not depend on it; threads beyond a CPU quota only slow it down (16-CPU quota: 1.41 s per Mb at 48, 0.98 s at 16)."""
+    n = int(os.environ.get("OMP_NUM_THREADS") or 0) or len(os.sched_getaffinity(0))
+    return max(1, min(48, n))
 
 
 def relaunch_ranks(n):
@@ -599,6 +620,63 @@ def bgzf_sample_check(N, B, w, q, output_format):
         s.close()
         gen.close()
     return gzip.decompress(outs[0]) == outs[1] and len(outs[1]) > 0
+
+
+DUMP_RUNS, DUMP_RUN_BYTES = 256, 16384      # seeded sample of the body: 256 runs of 16 KiB = 16 MB as float32
+DUMP_CHUNK = 1 << 20                         # the whole body as two sums per MiB: plain and position-weighted (exact in float64)
+
+
+def dump_outputs(outdir, eng, window, st, arena):
+    """--dump-outputs: what the last timed step computed, the body of `window` (VCF text or BCF2 records), as .npy files that two builds
+    can be compared on.  The timed path leaves its pages in the lanes' arenas, which the C ABI does not hand out, so the same window is
+    paged again from the same staged fragment (CombineEngine.pages, byte-identical to run_interval: test_pages_stay_in_hbm_*); its
+    length must equal the timed step's bytes_out.  Written: step_stats (float64: begin, end, num_cells, num_cells_in_window,
+    num_records, bytes_out, bytes_in_reference_cells), body_sample (float32 bytes of DUMP_RUNS runs at seeded offsets),
+    body_sample_offsets (float64) and body_chunk_sums (float64 [chunks, 2]: sum of the bytes of every MiB, and the same weighted by
+    1 + position mod 251)."""
+    import numpy as np
+    import torch
+    from genomicsdb_amd import synth
+    os.makedirs(outdir, exist_ok=True)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    total = int(st.bytes_out)
+    run = min(DUMP_RUN_BYTES, total)
+    starts = np.sort(np.random.default_rng(synth.SEED).integers(0, total - run + 1, size=DUMP_RUNS)) if total else np.zeros(0, np.int64)
+    idx = torch.from_numpy((starts[:, None] + np.arange(run)[None, :]).ravel()).to(dev)
+    sample = torch.zeros(idx.numel(), dtype=torch.uint8, device=dev)
+    nchunks = (total + DUMP_CHUNK - 1) // DUMP_CHUNK
+    sums = torch.zeros((nchunks, 2), dtype=torch.int64, device=dev)
+    weight = torch.arange(DUMP_CHUNK, dtype=torch.int64, device=dev) % 251 + 1
+    off = 0
+    for page in eng.page_tensors(window[0], window[1], arena_bytes=arena):
+        n = page.numel()
+        if off + n > total:
+            raise RuntimeError("--dump-outputs: the window's body is longer than the timed step's bytes_out (%d)" % total)
+        m = (idx >= off) & (idx < off + n)
+        sample[m] = page[idx[m] - off]
+        p = 0
+        while p < n:
+            c, r = divmod(off + p, DUMP_CHUNK)
+            if r or n - p < DUMP_CHUNK:        # a piece of one chunk (page boundaries fall anywhere)
+                ln = min(n - p, DUMP_CHUNK - r)
+                x = page[p:p + ln].to(torch.int64)
+                sums[c, 0] += x.sum()
+                sums[c, 1] += (x * weight[r:r + ln]).sum()
+            else:                               # whole chunks, up to 64 MiB at a time
+                k = min((n - p) // DUMP_CHUNK, 64)
+                ln = k * DUMP_CHUNK
+                x = page[p:p + ln].view(k, DUMP_CHUNK).to(torch.int64)
+                sums[c:c + k, 0] += x.sum(1)
+                sums[c:c + k, 1] += (x * weight).sum(1)
+            p += ln
+        off += n
+    if off != total:
+        raise RuntimeError("--dump-outputs: the window's body has %d bytes, the timed step wrote %d" % (off, total))
+    stats = [window[0], window[1], st.num_cells, st.num_cells_in_window, st.num_records, st.bytes_out, st.bytes_in_reference_cells]
+    np.save(os.path.join(outdir, "step_stats.npy"), np.array(stats, dtype=np.float64))
+    np.save(os.path.join(outdir, "body_sample.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(outdir, "body_sample_offsets.npy"), starts.astype(np.float64))
+    np.save(os.path.join(outdir, "body_chunk_sums.npy"), sums.cpu().numpy().astype(np.float64))
 
 
 def kernel_source_hash():

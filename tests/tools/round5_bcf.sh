@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 o=gpurun_out/r5t; mkdir -p $o
 timeout 900 python -m pytest tests -m gpu -x -q -k "bcf or lanes or format" 2>&1 | tail -3 | tee $o/tests_bcf.txt
 for l in 1 3; do
-  python bench.py --bcf --lanes $l --steps 6 --warmup 2 --no-cpu-baseline --no-c3 --no-stream > $o/bcf_l$l.json 2> $o/bcf_l$l.err
+  python bench.py --bcf --lanes $l --steps 6 --warmup 2 --full --no-cpu-baseline --no-c3 --no-stream > $o/bcf_l$l.json 2> $o/bcf_l$l.err
   python - "$o/bcf_l$l.json" "lanes=$l" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # Order as in round 4: the default bench line first on the fresh box, two idle minutes, then the profiler passes, then everything else.
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 o=gpurun_out/r5p; mkdir -p $o
-python bench.py > $o/bench_line.json 2> $o/bench.err
+python bench.py --full > $o/bench_line.json 2> $o/bench.err
 cut -c1-400 $o/bench_line.json
 python bench.py --lanes 1 --no-stream --no-c3 --no-cpu-baseline > $o/bench_line_lanes1.json 2> $o/bench_lanes1.err
 cut -c1-300 $o/bench_line_lanes1.json
@@ -13,7 +13,7 @@ sleep 30
 bash tests/tools/prof_traffic.sh r5p/traffic --steps 2 --warmup 1 --lanes 1 --no-stream --no-c3 > $o/traffic.log 2>&1
 bash tests/tools/prof_stats.sh r5p/stats_bcf --bcf --lanes 1 --steps 5 --warmup 1 --no-stream --no-c3 > $o/stats_bcf.log 2>&1; head -4 $o/stats_bcf.log
 bash tests/tools/prof_traffic.sh r5p/traffic_bcf --bcf --steps 2 --warmup 1 --lanes 1 --no-stream --no-c3 --no-alone-pass > $o/traffic_bcf.log 2>&1
-python bench.py --bcf --steps 6 --warmup 3 --no-cpu-baseline --no-c3 > $o/bench_bcf.json 2>/dev/null; cut -c1-300 $o/bench_bcf.json
+python bench.py --bcf --steps 6 --warmup 3 --full --no-cpu-baseline --no-c3 > $o/bench_bcf.json 2>/dev/null; cut -c1-300 $o/bench_bcf.json
 python bench.py --bcf --lanes 1 --steps 5 --warmup 1 --no-cpu-baseline --no-c3 --no-stream > $o/bench_bcf_lanes1.json 2>/dev/null; cut -c1-300 $o/bench_bcf_lanes1.json
 C5_LANES=1,2 timeout 900 python tests/tools/c5_full.py > $o/c5_full.json 2> $o/c5_full.err; cut -c1-400 $o/c5_full.json
 timeout 300 python __graft_entry__.py smoke > $o/smoke.log 2>&1; tail -2 $o/smoke.log
