@@ -216,6 +216,19 @@ class CombineEngine:
         _check(L.gdbamd_engine_print_cells(self._e, mode, buf, n) == n, "print_calls")
         return buf.raw[:n]
 
+    def query_variants(self):
+        """`gt_mpi_gather` without a mode flag / GenomicsDB::query_variants: the calls of the query's column intervals grouped into variants
+        (same begin, end, REF and set of ALT), GT and allele-length fields of multi-call variants in merged allele order, as the reference's
+        JSON document (print_variants' default format); selected, grouped and formatted on the device; bytes"""
+        L = _lib.lib()
+        L.gdbamd_engine_query_variants.restype = ctypes.c_int64
+        L.gdbamd_engine_query_variants.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        n = L.gdbamd_engine_query_variants(self._e, None, 0)
+        _check(n >= 0, "query_variants")
+        buf = ctypes.create_string_buffer(max(1, n))
+        _check(L.gdbamd_engine_query_variants(self._e, buf, n) == n, "query_variants")
+        return buf.raw[:n]
+
     def print_csv(self):
         return self.print_calls(1)
 

@@ -109,6 +109,12 @@ def build_hostsim():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "compat")])        # reference-shaped C++ caller (tests only)
 
 
+def build_hostsim_variants():
+    """CPU harness around the bodies of the variants query (core/gdb_variants.hpp; tests only)"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_variants")])
+    return os.path.join(ROOT, "tests", "hostsim_variants", "libhostsim_variants.so")
+
+
 if __name__ == "__main__":
     print(build_native(verbose=True))
     print(build_oracle())

@@ -330,6 +330,21 @@ int64_t gdbamd_engine_print_cells(void* engine, int mode, char* dst, uint64_t ca
     return (int64_t)n;
   } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
+// gt_mpi_gather without a mode flag: the variants document, same two-call convention (kept in the handle as "mode 3")
+int64_t gdbamd_engine_query_variants(void* engine, char* dst, uint64_t cap) {
+  try {
+    EngineHandle* h = (EngineHandle*)engine;
+    auto make = [&]() { h->calls_text_mode = 3; return h->eng->query_variants(); };
+    if (!dst) { h->calls_text = make(); return (int64_t)h->calls_text.size(); }
+    if (h->calls_text_mode != 3) h->calls_text = make();
+    const size_t n = h->calls_text.size();
+    if (cap < n) { g_last_error = "query_variants: destination too small"; return -1; }
+    memcpy(dst, h->calls_text.data(), n);
+    std::string().swap(h->calls_text);
+    h->calls_text_mode = -1;
+    return (int64_t)n;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
 // ColumnHistogramOperator::equi_partition_and_print_bins (variant_operations.cc:769-796), the text it prints; returns its length (dst may be NULL), -1 when
 // num_parts >= nbins (the reference prints a complaint and returns false)
 int64_t gdbamd_equi_partition_text(const uint64_t* counts, uint64_t nbins, uint64_t hist_begin, uint64_t bin_size, uint64_t num_parts, char* dst, uint64_t cap) {

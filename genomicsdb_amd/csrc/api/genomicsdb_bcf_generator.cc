@@ -400,7 +400,7 @@ void CombineEngine::for_each_interval_text(int mode, int arg, const std::functio
       const Coverage cov = cover(pos);
       m_pipe->set_array_rows(q2a);            // (cover() may have swapped the engine's two pipelines)
       const int64_t hi = std::min(cov.hi, iv.second);
-      text += m_pipe->cells_text(pos, hi, mode, arg, first_piece && !whole_array);
+      text += mode == 3 ? m_pipe->variants_text(pos, hi, first_piece && !whole_array) : m_pipe->cells_text(pos, hi, mode, arg, first_piece && !whole_array);   // (3: the variants query)
       first_piece = false;
       if (hi >= iv.second || m_src.kind == SRC_NONE || m_window_eof || cov.hi >= INT64_MAX - 1) break;
       pos = hi + 1;
@@ -423,6 +423,21 @@ std::string CombineEngine::print_calls() {
   });
   if (printed) o += "\n" + p1 + "]\n" + p0 + "}";
   o += "\n" + ip + "]\n}\n";
+  return o;
+}
+
+// gt_mpi_gather without a mode flag: print_variants' default format (variant.cc:983-999) around the variants of every query interval, one flat
+// list (the reference appends every interval's variants to one vector, tools/src/gt_mpi_gather.cc:102-132).  A group of calls never crosses a
+// begin column, so the pieces of a windowed source are grouped on their own like the intervals
+std::string CombineEngine::query_variants() {
+  std::string o = "{\n    \"variants\": [\n";
+  bool any = false;
+  for_each_interval_text(3, 0, [&](int64_t, int64_t, const std::string& t) {
+    if (t.empty()) return;
+    if (!any) o.append(t, 2, std::string::npos); else o += t;       // (every variant comes with ",\n" in front of it)
+    any = true;
+  });
+  o += "\n    ]\n}\n";
   return o;
 }
 

@@ -59,6 +59,8 @@ class CombineEngine {
   // gt_mpi_gather --print-calls (tools/src/gt_mpi_gather.cc:369-383): the JSON document of the query's cells, interval by interval
   // (VariantCallPrintOperator, variant_operations.cc:803-843); the cells are selected and formatted on the device (DevicePipeline::calls_json)
   std::string print_calls();
+  // gt_mpi_gather without a mode flag (GenomicsDB::query_variants): the calls of every query interval grouped into variants, as JSON
+  std::string query_variants();
   // --print-csv (VariantCallPrintCSVOperator, variant_operations.cc:845-903): one line per cell; --print-AC (AlleleCountOperator, :905-1089): per query
   // interval "column REF ALT count" of the normalised ALT alleles the cells' genotypes name, ordered by column, REF, ALT
   std::string print_csv();

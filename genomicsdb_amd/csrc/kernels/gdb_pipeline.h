@@ -133,6 +133,11 @@ class DevicePipeline {
   // "column<TAB>REF<TAB>ALT" per GT element naming an ALT allele, REF / ALT normalised (AlleleCountOperator, :951-1056; indent = the GT step);
   // mode 0 = the JSON objects with ",\n" in front of each
   std::string cells_text(int64_t qb, int64_t qe, int mode, int indent, bool with_intersecting);
+  // the variants query (gt_mpi_gather without a mode flag: VariantQueryProcessor::gt_get_column_interval + GA4GHOperator + Variant::print,
+  // core/gdb_variants.hpp): the selection of calls_json grouped into variants, every variant with ",\n" in front of it.  copy_out = false
+  // leaves the text in HBM (variants_text_bytes() says how much) and returns an empty string
+  std::string variants_text(int64_t qb, int64_t qe, bool with_intersecting, int64_t* ncalls = nullptr, int64_t* nvariants = nullptr, bool copy_out = true);
+  uint64_t variants_text_bytes() const;
   // the staged cells carry query rows; the printers above print array rows: the map (empty: identical)
   void set_array_rows(const std::vector<int64_t>& query_row_to_array_row);
   bool next_page(uint64_t arena_bytes, const char** dev_ptr, uint64_t* nbytes);

@@ -28,6 +28,7 @@
 #include "../core/gdb_stages.hpp"
 #include "../core/gdb_bcf.hpp"
 #include "../core/gdb_calls.hpp"
+#include "../core/gdb_variants.hpp"
 #include "gdb_pipeline.h"
 #include "gdb_bgzf.h"
 
@@ -3828,6 +3829,7 @@ struct DevicePipeline::Impl {
   DevBuf<uint32_t> site_key, site_key_sorted; DevBuf<int32_t> site_ord_in, site_ord;
   int ctx_slot = -1;                 // this pipeline's element of c_ex
   DevBuf<char> calls_names, calls_text; DevBuf<int32_t> calls_name_off; DevBuf<uint64_t> calls_len, calls_off; bool calls_names_ready = false; DevBuf<int64_t> calls_array_row; size_t calls_array_row_n = 0;   // --print-calls
+  DevBuf<int64_t> var_cell, var_end, var_iota, var_sorted, var_run, var_order; DevBuf<uint64_t> var_key, var_key_sorted, var_leader; uint64_t variants_bytes = 0;   // the variants query
   // persistent events (no create / destroy per interval) and one pinned block for every scalar that comes back to the host
   hipEvent_t ev_prep[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_page[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // per arena: start, before / after the page assembly, page done
@@ -5308,6 +5310,144 @@ std::string DevicePipeline::cells_text(int64_t qb, int64_t qe, int mode, int ind
   if (eb) throw GenomicsDBDeviceException(err_bits_text(eb));
   return out;
 }
+
+// ---- the variants query (gt_mpi_gather without a mode flag; core/gdb_variants.hpp) ----------------------------------------------------
+// select (the selection of k_calls, compacted: the cell order IS the reference's call order) -> 64-bit hash of (begin, end, REF, ALT set)
+// per call -> stable radix sort by hash -> first call with the same content inside a run of equal hashes = the variant's first call
+// (one comparison per call unless two keys collide) -> stable radix sort by that first call = variants in the order the reference opens
+// them, calls in reference order inside -> two-pass emit, one thread per call (a call remaps its own fields against the first call's ALT,
+// so a site that holds every sample of the cohort is as parallel as any other).
+__global__ void k_var_select(FragmentView fr, const int64_t* __restrict__ eff_end, int64_t c_base, int64_t n, int64_t qb, int64_t qe, int with_intersecting, uint64_t* __restrict__ take) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int64_t end = 0;
+  take[i] = calls_select(fr, eff_end, c_base + i, qb, qe, with_intersecting != 0, end) ? 1u : 0u;
+}
+__global__ void k_var_compact(FragmentView fr, CombinePlan pl, const int64_t* __restrict__ eff_end, int64_t c_base, int64_t n, int64_t qb, int64_t qe, int with_intersecting,
+                              const uint64_t* __restrict__ slot, int grouped, int64_t* __restrict__ call_cell, int64_t* __restrict__ call_end, uint64_t* __restrict__ hash,
+                              int64_t* __restrict__ iota, uint32_t* err) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int64_t end = 0;
+  if (!calls_select(fr, eff_end, c_base + i, qb, qe, with_intersecting != 0, end)) return;
+  const int64_t k = (int64_t)slot[i];
+  uint32_t e = 0;
+  call_cell[k] = c_base + i; call_end[k] = end; iota[k] = k;
+  hash[k] = grouped ? var_call_hash(fr, pl, c_base + i, end, &e) : (uint64_t)k;
+  if (e) atomicOr(err, e);
+}
+__global__ void k_var_run_heads(const uint64_t* __restrict__ sorted_hash, int64_t n, int64_t* __restrict__ head) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  head[p] = (p == 0 || sorted_hash[p] != sorted_hash[p - 1]) ? p : 0;
+}
+__global__ void k_var_leader(FragmentView fr, CombinePlan pl, const int64_t* __restrict__ call_cell, const int64_t* __restrict__ call_end, const int64_t* __restrict__ sorted,
+                             const int64_t* __restrict__ run_start, int64_t n, uint64_t* __restrict__ leader) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  leader[sorted[p]] = (uint64_t)var_find_leader(fr, pl, call_cell, call_end, sorted, run_start, p);
+}
+template <bool WRITE> __global__ void k_var_emit(FragmentView fr, CombinePlan pl, QueryWindow qw, CallsNames names, const int64_t* __restrict__ call_cell, const int64_t* __restrict__ call_end,
+                                                 const uint64_t* __restrict__ sorted_leader, const int64_t* __restrict__ order, int64_t n, uint64_t* __restrict__ len_or_off,
+                                                 char* __restrict__ out, uint32_t* err) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int64_t i = order[k];
+  const uint64_t lead = sorted_leader[k];
+  const bool first = k == 0 || sorted_leader[k - 1] != lead, last = k + 1 == n || sorted_leader[k + 1] != lead;
+  uint32_t e = 0;
+  if (!WRITE) {
+    CountSink s;
+    variants_emit_call(s, fr, pl, qw, names, call_cell[i], call_end[i], call_cell[lead], first, last, &e);
+    len_or_off[k] = s.n;
+  } else {
+    ByteSink s(out + len_or_off[k]);
+    variants_emit_call(s, fr, pl, qw, names, call_cell[i], call_end[i], call_cell[lead], first, last, &e);
+  }
+  if (e) atomicOr(err, e);
+}
+
+std::string DevicePipeline::variants_text(int64_t qb, int64_t qe, bool with_intersecting, int64_t* ncalls, int64_t* nvariants, bool copy_out) {
+  Impl& S = *m_;
+  HIP_CHECK(hipSetDevice(S.device));
+  hipStream_t st = S.stream;
+  const FragmentView& fr = S.fr;
+  const CombinePlan& pl = S.hp.plan;
+  const int64_t C = fr.ncells;
+  if (ncalls) *ncalls = 0;
+  if (nvariants) *nvariants = 0;
+  S.variants_bytes = 0;
+  if (C == 0 || pl.num_query_rows == 0) return std::string();
+  for (int f = 0; f < pl.nfields; ++f)
+    if (pl.field[f].ndim == 2) throw GenomicsDBDeviceException("query_variants: 2-dimensional field " + S.hp.field_names[(size_t)f] + " is not printed on the device");
+  HIP_CHECK(hipMemsetAsync(S.err.p, 0, sizeof(uint32_t), st));
+  classify_fragment();
+  if (!S.calls_names_ready) {
+    std::string text; std::vector<int32_t> off;
+    for (const auto& nm : S.hp.field_names) { off.push_back((int32_t)text.size()); text += nm; }
+    off.push_back((int32_t)text.size());
+    S.calls_names.ensure(text.size() + 1); S.calls_name_off.ensure(off.size());
+    HIP_CHECK(hipMemcpy(S.calls_names.p, text.data(), text.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(S.calls_name_off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    S.calls_names_ready = true;
+  }
+  S.cwin.ensure(4);
+  hipLaunchKernelGGL(k_cell_window, dim3(1), dim3(64), 0, st, fr.begin, C, qb > INT64_MIN + S.max_span ? qb - S.max_span : INT64_MIN, qe, S.cwin.p);
+  int64_t cw[2] = {0, 0};
+  S.read_back_many({{cw, S.cwin.p, 2 * sizeof(int64_t)}});
+  const int64_t c_base = cw[0], CW = cw[1] - cw[0];
+  if (CW <= 0) return std::string();
+  const int wi = with_intersecting ? 1 : 0;
+  const int64_t* eff = S.eff_end.p;
+  // select + compact
+  S.calls_len.ensure((size_t)CW + 1); S.calls_off.ensure((size_t)CW + 1);
+  hipLaunchKernelGGL(k_var_select, dim3(blocks_for(CW)), dim3(kBlock), 0, st, fr, eff, c_base, CW, qb, qe, wi, S.calls_len.p);
+  HIP_CHECK(hipMemsetAsync(S.calls_len.p + CW, 0, sizeof(uint64_t), st));
+  S.excl_scan(S.calls_len.p, S.calls_off.p, (size_t)CW + 1);
+  const int64_t n = (int64_t)S.read_back(S.calls_off.p + CW);
+  if (n == 0) return std::string();
+  const bool grouped = pl.f_REF >= 0 && pl.f_ALT >= 0;      // (without REF or ALT among the attributes every call is a variant of its own)
+  S.var_cell.ensure((size_t)n); S.var_end.ensure((size_t)n); S.var_iota.ensure((size_t)n); S.var_sorted.ensure((size_t)n); S.var_run.ensure((size_t)n); S.var_order.ensure((size_t)n);
+  S.var_key.ensure((size_t)n); S.var_key_sorted.ensure((size_t)n); S.var_leader.ensure((size_t)n);
+  hipLaunchKernelGGL(k_var_compact, dim3(blocks_for(CW)), dim3(kBlock), 0, st, fr, pl, eff, c_base, CW, qb, qe, wi, (const uint64_t*)S.calls_off.p, grouped ? 1 : 0, S.var_cell.p, S.var_end.p,
+                     S.var_key.p, S.var_iota.p, S.err.p);
+  const uint64_t* sorted_leader = S.var_key.p;               // not grouped: leader = the call itself, already in order
+  const int64_t* order = S.var_iota.p;
+  if (grouped) {
+    S.sort_pairs(S.var_key.p, S.var_key_sorted.p, S.var_iota.p, S.var_sorted.p, (size_t)n, 64);
+    hipLaunchKernelGGL(k_var_run_heads, dim3(blocks_for(n)), dim3(kBlock), 0, st, (const uint64_t*)S.var_key_sorted.p, n, S.var_run.p);
+    S.incl_scan(S.var_run.p, S.var_run.p, (size_t)n, rocprim::maximum<int64_t>());
+    hipLaunchKernelGGL(k_var_leader, dim3(blocks_for(n)), dim3(kBlock), 0, st, fr, pl, (const int64_t*)S.var_cell.p, (const int64_t*)S.var_end.p, (const int64_t*)S.var_sorted.p,
+                       (const int64_t*)S.var_run.p, n, S.var_leader.p);
+    S.sort_pairs(S.var_leader.p, S.var_key_sorted.p, S.var_iota.p, S.var_order.p, (size_t)n, std::max(1, bits_for((uint64_t)n)));
+    sorted_leader = S.var_key_sorted.p; order = S.var_order.p;
+  }
+  // emit
+  QueryWindow qw;
+  memset(&qw, 0, sizeof(qw));
+  qw.qb = qb; qw.qe = qe;
+  qw.contigs = S.contigs.p; qw.ncontigs = (int32_t)S.hp.contigs.size(); qw.contig_names = S.contig_names.p;
+  CallsNames names{S.calls_names.p, S.calls_name_off.p, S.calls_array_row_n ? S.calls_array_row.p : nullptr};
+  S.calls_len.ensure((size_t)n + 1); S.calls_off.ensure((size_t)n + 1);
+  hipLaunchKernelGGL(k_var_emit<false>, dim3(blocks_for(n)), dim3(kBlock), 0, st, fr, pl, qw, names, (const int64_t*)S.var_cell.p, (const int64_t*)S.var_end.p, sorted_leader, order, n,
+                     S.calls_len.p, (char*)nullptr, S.err.p);
+  HIP_CHECK(hipMemsetAsync(S.calls_len.p + n, 0, sizeof(uint64_t), st));
+  S.excl_scan(S.calls_len.p, S.calls_off.p, (size_t)n + 1);
+  const uint64_t total = S.read_back(S.calls_off.p + n);
+  S.calls_text.ensure((size_t)total + 16);
+  hipLaunchKernelGGL(k_var_emit<true>, dim3(blocks_for(n)), dim3(kBlock), 0, st, fr, pl, qw, names, (const int64_t*)S.var_cell.p, (const int64_t*)S.var_end.p, sorted_leader, order, n,
+                     S.calls_off.p, S.calls_text.p, S.err.p);
+  std::string out;
+  if (copy_out) { out.assign((size_t)total, '\0'); HIP_CHECK(hipMemcpyAsync(&out[0], S.calls_text.p, (size_t)total, hipMemcpyDeviceToHost, st)); }
+  uint32_t eb = 0;
+  S.read_back_many({{&eb, S.err.p, sizeof(uint32_t)}});
+  if (eb) throw GenomicsDBDeviceException(err_bits_text(eb));
+  S.variants_bytes = total;
+  if (ncalls) *ncalls = n;
+  if (nvariants) { size_t k = 0; const std::string head = ",\n        {\n"; for (size_t q = out.find(head); q != std::string::npos; q = out.find(head, q + 1)) ++k; *nvariants = (int64_t)k; }
+  return out;
+}
+uint64_t DevicePipeline::variants_text_bytes() const { return m_->variants_bytes; }
 
 // the sizing / resolution pass of `n` records in `order` (piece-wise kernel by default; GDBAMD_SIZE3=0: the record-by-record one).
 // size_slots: elements of chunk_size (the check mode compares them all)

@@ -1,5 +1,7 @@
-// gt_mpi_gather - command line of the reference's query tool for the one mode this build implements:
-//   gt_mpi_gather -j <query.json> [-l <loader.json>] [-r <rank>] [-p <page size>] [-s <segment size>] [-O <fmt>] --produce-Broad-GVCF
+// gt_mpi_gather - command line of the reference's query tool:
+//   gt_mpi_gather -j <query.json> [-l <loader.json>] [-r <rank>] [-p <page size>] [-s <segment size>] [-O <fmt>] [--produce-Broad-GVCF | ...]
+// Without a mode flag it answers the variants query (gt_get_column_interval + print_variants, tools/src/gt_mpi_gather.cc:102-132, 294): the
+// document of this rank's column partition goes to stdout; the reference's MPI gather of all ranks' variants to rank 0 is not rebuilt.
 // (reference: tools/src/gt_mpi_gather.cc:437-531; scan_and_produce_Broad_GVCF :322-366).  One process per column partition
 // like `mpirun -n P gt_mpi_gather`: the rank comes from -r, else from the launcher (OMPI_COMM_WORLD_RANK / PMI_RANK / RANK);
 // ranks do not communicate.  The VCF goes to "vcf_output_filename" of the query JSON (per-rank entry if it is a list), else to
@@ -58,13 +60,30 @@ int main(int argc, char** argv) {
       case ARGS_IDX_PRINT_CSV: print_calls = true; print_mode = 1; break;
       case ARGS_IDX_PRINT_AC: print_calls = true; print_mode = 2; break;
       case ARGS_IDX_VERSION: std::cout << "genomicsdb_amd (MI355X variant-combine path) for GenomicsDB 0.10.2 query JSON\n"; return 0;
-      case ARGS_IDX_UNSUPPORTED: std::cerr << "this build implements --produce-Broad-GVCF, --produce-histogram, --print-calls, --print-csv and --print-AC only\n"; return -1;
+      case ARGS_IDX_UNSUPPORTED: std::cerr << "this build implements the variants query (no mode flag), --produce-Broad-GVCF, --produce-histogram, --print-calls, --print-csv and --print-AC only\n"; return -1;
       default: std::cerr << "Unknown command line argument\n"; return -1;
     }
   }
-  if (json_config.empty() || !(produce_gvcf || produce_histogram || print_calls)) {
-    std::cerr << "Usage: gt_mpi_gather -j <query.json> [-l <loader.json>] [-r rank] [-p page_size] [-O output_format] --produce-Broad-GVCF | --produce-histogram | --print-calls | --print-csv | --print-AC\n";
+  if (json_config.empty()) {
+    std::cerr << "Usage: gt_mpi_gather -j <query.json> [-l <loader.json>] [-r rank] [-p page_size] [-O output_format] [--produce-Broad-GVCF | --produce-histogram | --print-calls | --print-csv | --print-AC]\n"
+                 "without a mode flag: the variants of the query intervals as JSON on stdout, one process per column partition (the ranks' documents are not gathered to rank 0)\n";
     return -1;
+  }
+  if (!(produce_gvcf || produce_histogram || print_calls)) {
+    // the default command (tools/src/gt_mpi_gather.cc:102-132): gt_get_column_interval per query interval, print_variants' default format; grouped and printed on the GPU
+    if (output_format == "Cotton-JSON" || output_format == "Positions-JSON" || output_format == "GA4GH") {
+      std::cerr << "gt_mpi_gather: output format " << output_format << " of the variants query is not implemented by this build (default JSON format only)\n";
+      return -1;
+    }
+    try {
+      GenomicsDBBCFGenerator gen(loader_json, json_config, "", 0, 0, rank, (size_t)1u << 20, segment_size, "", true, false, true);
+      const std::string doc = gen.engine().query_variants();
+      fwrite(doc.data(), 1, doc.size(), stdout);
+    } catch (const std::exception& e) {
+      std::cerr << "gt_mpi_gather: " << e.what() << "\n";
+      return -1;
+    }
+    return 0;
   }
   if (print_calls) {
     // print_calls, COMMAND_PRINT_CALLS (tools/src/gt_mpi_gather.cc:369-383): the cells of the query intervals as JSON; selected and formatted on the GPU

@@ -157,6 +157,12 @@ int64_t gdbamd_engine_print_calls(void* engine, char* dst, uint64_t cap);
  * "column REF ALT count" per normalised ALT allele named by a genotype, per query interval in the order of column, REF, ALT).  The reference's tests
  * hold no golden for modes 1 and 2: parity is against the oracle's restatement only. */
 int64_t gdbamd_engine_print_cells(void* engine, int mode, char* dst, uint64_t cap);
+/* The variants query - what the reference's gt_mpi_gather prints without a mode flag and GenomicsDB::query_variants users get
+ * (VariantQueryProcessor::gt_get_column_interval, src/main/cpp/src/genomicsdb/query_variants.cc:687-843; print_variants' default format, variant.cc:983-999):
+ * per query interval the calls that cover its begin and the cells that begin inside, grouped into variants by (begin, end, REF, set of ALT), GT and the
+ * allele-length fields of a variant with several calls rewritten in merged allele order (GA4GHOperator).  Selected, grouped and formatted on the device.
+ * Same calling convention as gdbamd_engine_print_cells.  -1: error. */
+int64_t gdbamd_engine_query_variants(void* engine, char* dst, uint64_t cap);
 /* "index_output_VCF" (src/main/cpp/src/config/json_config.cc:648, src/main/cpp/src/vcf/vcf_adapter.cc:275-295): the index htslib builds from a finished BGZF
  * file - <path>.tbi for a bgzip'ed VCF (tbx_index_build with the VCF preset), <path>.csi with min_shift 14 for a BGZF BCF2 file (bcf_index_build(.., 14)).
  * The file-writing VCFAdapter and gt_mpi_gather call it when the query JSON says "index_output_VCF": true and the format is "z" / "b". */
