@@ -354,15 +354,30 @@ def unpin_host_memory(addr):
     _check(_lib.lib().gdbamd_unpin_host_memory(addr) == 0, "unpin_host_memory")
 
 
-def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_deletions_as_intervals=True, column_begin=0, column_end=2**63 - 2):
+IMPORT_STAT_NAMES = ("num_files", "num_records", "num_cells", "num_spanning_cells", "num_bytes", "num_deferred_values", "num_batches", "text_bytes",
+                     "ms_index", "ms_measure", "ms_write", "ms_sort_gather", "s_read", "s_h2d", "s_deferred", "s_d2h", "s_total")
+
+
+def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_deletions_as_intervals=True, column_begin=0, column_end=2**63 - 2,
+                 device=None, text_budget_bytes=0, stats=None):
     """(g)VCFs of a callset mapping -> begin-cells (bytes, reference binary cell layout, column-major) of one column partition:
-    the conversion step of the reference's vcf2tiledb (vcf2binary.cc:991-1196).  Host code, no device needed."""
+    the conversion step of the reference's vcf2tiledb (vcf2binary.cc:991-1196).
+    device=None: host code, no device needed.  device=<int>: the conversion runs on that GPU (kernels/gdb_import.hip) and gives
+    the same bytes; text_budget_bytes is the record text per batch (0: default) and `stats`, a dict, receives IMPORT_STAT_NAMES."""
     L = _lib.lib()
     p = ctypes.c_void_p()
     n = ctypes.c_uint64()
     nc = ctypes.c_int64()
-    rc = L.gdbamd_import_cells(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), 1 if treat_deletions_as_intervals else 0,
-                               column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc))
+    if device is None:
+        rc = L.gdbamd_import_cells(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), 1 if treat_deletions_as_intervals else 0,
+                                   column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc))
+    else:
+        st = (ctypes.c_double * len(IMPORT_STAT_NAMES))()
+        rc = L.gdbamd_import_cells_device(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
+                                          1 if treat_deletions_as_intervals else 0, column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc),
+                                          int(device), int(text_budget_bytes), st)
+        if rc == 0 and stats is not None:
+            stats.update({k: (float(v) if k[:2] in ("ms", "s_") else int(v)) for k, v in zip(IMPORT_STAT_NAMES, st)})
     _check(rc == 0, "import_cells")
     try:
         return ctypes.string_at(p.value, n.value), nc.value

@@ -18,6 +18,7 @@ TOOLS = {"gt_mpi_gather": TOOL, "vcf2tiledb": os.path.join(PKG, "vcf2tiledb")}
 SOURCES = [
     "kernels/gdb_pipeline.hip",
     "kernels/gdb_bgzf.hip",
+    "kernels/gdb_import.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -113,6 +114,12 @@ def build_hostsim_variants():
     """CPU harness around the bodies of the variants query (core/gdb_variants.hpp; tests only)"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_variants")])
     return os.path.join(ROOT, "tests", "hostsim_variants", "libhostsim_variants.so")
+
+
+def build_hostsim_import():
+    """CPU harness around the bodies of the device importer (core/gdb_import.hpp; tests only)"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_import")])
+    return os.path.join(ROOT, "tests", "hostsim_import", "libhostsim_import.so")
 
 
 if __name__ == "__main__":

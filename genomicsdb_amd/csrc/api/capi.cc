@@ -417,6 +417,36 @@ int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mappin
     return 0;
   } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
+int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                               int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
+                               double* stats) {
+  try {
+    if (!vid_mapping_file || !callset_mapping_file || !cells || !nbytes) throw GenomicsDBConfigException("gdbamd_import_cells_device: null argument");
+    VidMapper vid;
+    vid.parse_vid_json(mini_json::parse_file(vid_mapping_file));
+    vid.parse_callsets_json(mini_json::parse_file(callset_mapping_file));
+    ImportOptions opt;
+    opt.treat_deletions_as_intervals = treat_deletions_as_intervals != 0;
+    opt.column_begin = column_begin;
+    opt.column_end = column_end;
+    if (file_root) opt.file_root = file_root;
+    ImportStats st;
+    const std::vector<uint8_t> out = import_callsets_to_cells_device(vid, opt, device, text_budget_bytes, &st);
+    *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
+    if (!*cells) throw GenomicsDBConfigException("out of memory");
+    if (!out.empty()) memcpy(*cells, out.data(), out.size());
+    *nbytes = out.size();
+    if (ncells) *ncells = st.num_cells;
+    if (stats) {
+      const double v[GDBAMD_IMPORT_NUM_STATS] = {(double)st.num_files, (double)st.num_records, (double)st.num_cells, (double)st.num_spanning_cells, (double)st.num_bytes,
+                                                 (double)st.num_deferred_values, (double)st.num_batches, (double)st.text_bytes, st.ms_index, st.ms_measure, st.ms_write,
+                                                 st.ms_sort_gather, st.s_read, st.s_h2d, st.s_deferred, st.s_d2h, st.s_total};
+      memcpy(stats, v, sizeof(v));
+    }
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
 void gdbamd_free(void* p) { free(p); }
 
 }  // extern "C"

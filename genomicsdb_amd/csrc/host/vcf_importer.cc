@@ -205,6 +205,9 @@ struct Cell { int64_t row, col; size_t off, len; };
 
 }  // namespace
 
+int64_t import_parse_int(const char* p, size_t n, const std::string& what) { return parse_int(Tok{p, n}, what); }
+double import_parse_double(const char* p, size_t n, const std::string& what) { return parse_double(Tok{p, n}, what); }
+
 std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const ImportOptions& opt, ImportStats* stats) {
   if (!vid.is_initialized() || !vid.is_callset_mapping_initialized()) throw VCF2BinaryException("vid and callset mappings are needed");
   // attribute order of the schema (same walk as VidMapper::schema_attribute_names)

@@ -11,8 +11,10 @@
 //          [INFO attributes in vid order][FORMAT attributes in vid order]
 //          fixed-length attribute = num x element (missing: TileDB null), var-length = i32 num + num x element (missing: num 0)
 //
-// Not done (documented in DESIGN.md): htslib's record-level checks, CSV / buffer-stream inputs, intervals that cross a column
-// partition boundary (a cell belongs to the partition of its begin column), multi-dimensional (allele-specific) fields.
+// Not done (documented in DESIGN.md): htslib's record-level checks, CSV / buffer-stream inputs, fields of more than 2
+// dimensions.  2-dimensional (allele-specific) fields and intervals that reach across a partition begin ARE imported by
+// import_callsets_to_cells; the device path (import_callsets_to_cells_device, kernels/gdb_import.hip) refuses 2-dimensional
+// fields and flattened tuple elements by name and leaves those vids to the host importer.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -33,9 +35,27 @@ struct ImportOptions {
   int64_t column_begin = 0, column_end = INT64_MAX - 1;   // column partition: cells that begin inside are kept
   std::string file_root;                           // prefix of relative "filename" entries of the callset mapping
 };
-struct ImportStats { int64_t num_files = 0, num_records = 0, num_cells = 0, num_spanning_cells = 0; uint64_t num_bytes = 0; };   // num_spanning_cells: intervals replayed at the partition begin
+struct ImportStats {
+  int64_t num_files = 0, num_records = 0, num_cells = 0, num_spanning_cells = 0; uint64_t num_bytes = 0;   // num_spanning_cells: intervals replayed at the partition begin
+  // device path only
+  int64_t num_deferred_values = 0;     // numeric tokens outside the device's exact fast path, parsed by the host functions
+  int64_t num_batches = 0; uint64_t text_bytes = 0;
+  float ms_index = 0, ms_measure = 0, ms_write = 0, ms_sort_gather = 0;      // HIP-event time per phase, summed over the batches
+  double s_read = 0, s_h2d = 0, s_deferred = 0, s_d2h = 0, s_total = 0;     // wall clock: file read + inflate, text upload, host parsing of deferred tokens, result download
+};
 
 // every callset of vid's callset mapping (file, idx_in_file, row_idx); cells in column-major (column, row) order
 std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const ImportOptions& opt, ImportStats* stats = nullptr);
+
+// The same bytes, made on GPU `device` (kernels/gdb_import.hip): the host reads and inflates the files and maps the samples,
+// the device indexes, measures, writes, sorts and gathers the cells.  text_budget_bytes: record text per batch (0: default).
+// Refuses, before any launch, 2-dimensional fields, flattened tuple elements and what import_callsets_to_cells refuses.
+std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes,
+                                                     ImportStats* stats = nullptr);
+
+// the importer's number parsers (strtoll / strtod over the whole token, VCF2BinaryException otherwise): the device path runs
+// them on the tokens it deferred
+int64_t import_parse_int(const char* p, size_t n, const std::string& what);
+double import_parse_double(const char* p, size_t n, const std::string& what);
 
 }  // namespace genomicsdb_amd

@@ -1,0 +1,35 @@
+// gdb_import.h - the device importer: (g)VCF record text -> begin-cells on one GPU (host-visible interface, no HIP types).
+//
+// The host reads and inflates a file, maps its samples to rows from the #CHROM line and hands the record text over in batches of at
+// most `text_budget_bytes`, cut at a newline.  Per batch the device indexes newlines and tabs, measures one cell per
+// (record line, imported sample), lays the cells out by a scan and writes them - the bodies of core/gdb_import.hpp, the same
+// bytes as host/vcf_importer.cc.  finish() resolves the intervals that span the partition begin, sorts all cells by
+// (column, row) with ties in append order, gathers them into column-major order and copies the result out once.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../host/vcf_importer.h"
+#include "../host/vid_mapper.h"
+
+namespace genomicsdb_amd {
+
+class DeviceImporter {
+ public:
+  static constexpr uint64_t kDefaultTextBudget = (uint64_t)64 << 20;
+  // refuses (VCF2BinaryException) what the bodies do not cover before anything is launched
+  DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes = 0);
+  ~DeviceImporter();
+  DeviceImporter(const DeviceImporter&) = delete;
+  DeviceImporter& operator=(const DeviceImporter&) = delete;
+  void import_all();                                  // append_file for every file of the callset mapping, in mapping order
+  void append_file(const std::string& filename);      // a "filename" of the callset mapping
+  void finish(std::vector<uint8_t>& cells);
+  const ImportStats& stats() const;
+ private:
+  struct Impl;
+  Impl* m_;
+};
+
+}  // namespace genomicsdb_amd

@@ -1,0 +1,612 @@
+// gdb_import.hip - see gdb_import.h.  Kernels for gfx950 around the bodies of core/gdb_import.hpp, and their orchestration.
+//
+// Per batch of record text (all launches on one stream):
+//   index    k_imp_count: newlines and tabs per 4 KiB tile -> rocPRIM exclusive scan of the tile counts -> k_imp_scatter: positions
+//            of the newlines and the tabs plus, per line, the number of tabs in front of it, so (line, column k) -> byte offset is O(1)
+//   measure  k_imp_measure: one thread per (line, imported sample): coordinates, partition filter, cell size, errors, the packed
+//            atomicMax (column, line sequence number) per row for the partition-begin rule
+//   layout   rocPRIM exclusive scan of the sizes
+//   write    k_imp_write: the same grid emits the cells, the deferred-token list and the 64-bit sort key (column, row) per slot
+// finish():  k_imp_resolve drops the spanning candidates that are not their row's choice, a stable rocPRIM radix sort of the keys
+//            over the slots of all batches (slots are in the host importer's append order, so ties resolve as std::stable_sort
+//            does), k_imp_gather copies the variable-size cells into column-major order, one copy to the host.
+#include "gdb_import.h"
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+
+#include "../common/gz_text.hpp"
+#include "../host/import_common.hpp"
+#include "gdb_pipeline.h"
+
+namespace genomicsdb_amd {
+
+#define IMP_HIP_CHECK(expr)                                                                                        \
+  do {                                                                                                             \
+    hipError_t _e = (expr);                                                                                        \
+    if (_e != hipSuccess)                                                                                          \
+      throw GenomicsDBDeviceException(std::string(#expr) + " failed: " + hipGetErrorString(_e) + " at " + __FILE__ + ":" + std::to_string(__LINE__)); \
+  } while (0)
+
+namespace {
+using namespace gdbimp;
+
+constexpr int kBlock = 256;              // 4 wavefronts
+constexpr int kBytesPerThread = 16;      // one 16-byte load
+constexpr uint32_t kTile = kBlock * kBytesPerThread;
+constexpr uint32_t kTextPad = 64;        // bytes behind the text that the 16-byte loads may touch
+constexpr int kErrWords = 16;            // [0]: ImpErr bits, [1 + b]: smallest line that raised bit b
+constexpr uint64_t kDroppedKey = ~(uint64_t)0;
+
+struct ImpBatch { const char* text; const uint32_t* nl_pos; const uint32_t* line_first_tab; const uint32_t* tab_pos; uint32_t n_lines; };
+
+// counts of one thread's 16 bytes: newlines in the high word, tabs in the low word
+__device__ __forceinline__ uint64_t imp_count16(const char* text, uint32_t n, uint64_t at, uint4* bytes) {
+  *bytes = *reinterpret_cast<const uint4*>(text + at);     // (the buffer is padded: at + 16 <= n + kTextPad)
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(bytes);
+  uint32_t nl = 0, tab = 0;
+#pragma unroll
+  for (int i = 0; i < kBytesPerThread; ++i) {
+    const bool in = at + (uint64_t)i < (uint64_t)n;
+    nl += in && b[i] == '\n';
+    tab += in && b[i] == '\t';
+  }
+  return ((uint64_t)nl << 32) | tab;
+}
+
+__global__ void __launch_bounds__(kBlock) k_imp_count(const char* text, uint32_t n, uint64_t* tile_counts) {
+  __shared__ unsigned long long s_count;
+  if (threadIdx.x == 0) s_count = 0;
+  __syncthreads();
+  const uint64_t at = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kBytesPerThread;
+  uint64_t c = 0;
+  uint4 bytes;
+  if (at < n) c = imp_count16(text, n, at, &bytes);
+  if (c) atomicAdd(&s_count, (unsigned long long)c);
+  __syncthreads();
+  if (threadIdx.x == 0) tile_counts[blockIdx.x] = s_count;
+}
+
+__global__ void __launch_bounds__(kBlock) k_imp_scatter(const char* text, uint32_t n, const uint64_t* tile_base, uint32_t* nl_pos, uint32_t* line_first_tab,
+                                                       uint32_t* tab_pos, uint32_t n_lines, uint32_t n_tabs) {
+  __shared__ uint64_t s_scan[kBlock];
+  const uint64_t at = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kBytesPerThread;
+  uint4 bytes = make_uint4(0, 0, 0, 0);
+  const uint64_t mine = at < n ? imp_count16(text, n, at, &bytes) : 0;
+  s_scan[threadIdx.x] = mine;
+  __syncthreads();
+  for (int d = 1; d < kBlock; d <<= 1) {       // inclusive scan over the block
+    const uint64_t add = (int)threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0;
+    __syncthreads();
+    s_scan[threadIdx.x] += add;
+    __syncthreads();
+  }
+  if (!mine) return;
+  const uint64_t before = tile_base[blockIdx.x] + s_scan[threadIdx.x] - mine;
+  uint32_t nl = (uint32_t)(before >> 32), tab = (uint32_t)before;
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(&bytes);
+  for (int i = 0; i < kBytesPerThread; ++i) {
+    if (at + (uint64_t)i >= (uint64_t)n) break;
+    if (b[i] == '\n') { if (nl < n_lines) { nl_pos[nl] = (uint32_t)at + i; line_first_tab[nl + 1u] = tab; } ++nl; }
+    else if (b[i] == '\t') { if (tab < n_tabs) tab_pos[tab] = (uint32_t)at + i; ++tab; }
+  }
+}
+
+__device__ __forceinline__ ImpLine imp_line_of(const ImpBatch& B, uint32_t line) {
+  ImpLine L;
+  L.text = B.text;
+  L.begin = line ? B.nl_pos[line - 1u] + 1u : 0u;
+  L.end = B.nl_pos[line];
+  if (L.end > L.begin && B.text[L.end - 1u] == '\r') --L.end;
+  const uint32_t first = B.line_first_tab[line];
+  L.tabs = B.tab_pos + first;
+  L.ntabs = B.line_first_tab[line + 1u] - first;
+  return L;
+}
+
+__device__ __forceinline__ void imp_raise(uint32_t* err, uint32_t bits, uint32_t line) {
+  atomicOr(&err[0], bits);
+  for (uint32_t b = 0; b < (uint32_t)kErrWords - 1u; ++b) if (bits & (1u << b)) atomicMin(&err[1u + b], line);
+}
+
+struct ImpSamples { const int32_t* file_idx; const int64_t* row; int32_t n; };    // imported samples of the file
+struct ImpSpan { unsigned long long* row_best; int32_t seq_bits; uint64_t line_seq_base; int64_t max_row; };   // row_best null: no partition begin
+
+// one thread per (record line, imported sample); with no imported sample one thread per line, for the checks and the count
+__global__ void __launch_bounds__(kBlock) k_imp_measure(ImpTables T, ImpBatch B, ImpSamples S, ImpSpan P, uint64_t n_slots, int64_t* col, int64_t* end,
+                                                       uint64_t* size, uint8_t* kind, uint32_t* err, unsigned long long* counters) {
+  const uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t per_line = S.n > 0 ? (uint32_t)S.n : 1u;
+  bool is_record = false, is_cell = false;
+  if (slot < n_slots) {
+    const uint32_t line = (uint32_t)(slot / per_line), j = (uint32_t)(slot % per_line);
+    const ImpLine L = imp_line_of(B, line);
+    const int sample = S.n > 0 ? S.file_idx[j] : -1;
+    const ImpSlot s = imp_measure(T, L, sample);
+    is_record = j == 0u && L.end > L.begin && B.text[L.begin] != '#';
+    if (s.err) imp_raise(err, s.err, line);
+    else if (P.row_best && sample >= 0 && L.end > L.begin && B.text[L.begin] != '#' && s.col <= T.column_end && s.col <= T.column_begin) {
+      const int64_t row = S.row[j];
+      if (row >= 0 && row <= P.max_row)
+        atomicMax(&P.row_best[row], ((unsigned long long)s.col << P.seq_bits) | (unsigned long long)(P.line_seq_base + line + 1u));
+    }
+    col[slot] = s.col; end[slot] = s.end; size[slot] = s.err ? 0u : s.size; kind[slot] = s.err ? (uint8_t)IMP_SLOT_NONE : (uint8_t)s.kind;
+    is_cell = !s.err && s.kind != IMP_SLOT_NONE;
+  }
+  const unsigned long long rec = __ballot(is_record), cel = __ballot(is_cell);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (rec) atomicAdd(&counters[0], (unsigned long long)__popcll(rec));
+    if (cel) atomicAdd(&counters[1], (unsigned long long)__popcll(cel));
+  }
+}
+
+constexpr uint32_t kStageBytes = 64u << 10;   // LDS a block may stage its cells in (gfx950: 160 KiB per CU, so two blocks fit)
+
+// The slots of a block are consecutive, so its cells are one contiguous byte range of the batch's cell buffer.  STAGE: the threads
+// write their cells - byte by byte, as the bodies do - into LDS at the range's own alignment, and the block then stores the range
+// with aligned dwords, consecutive lanes on consecutive words; a block whose cells do not fit writes them directly like STAGE = false
+// (profiles/device_import.md has the A/B).
+template <bool STAGE>
+__global__ void __launch_bounds__(kBlock) k_imp_write(ImpTables T, ImpBatch B, ImpSamples S, ImpSpan P, uint64_t n_slots, const int64_t* col, const int64_t* end,
+                                                     const uint64_t* size, const uint8_t* kind, const uint64_t* off, uint8_t* cells, uint64_t cells_bytes,
+                                                     ImpDeferred* def, uint32_t* ndef, uint32_t def_cap, uint64_t* key_out, uint64_t* src_out, uint32_t* size_out,
+                                                     uint64_t* tag_out, uint32_t* err) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_stage[STAGE ? kStageBytes : 16];
+  const uint64_t first = (uint64_t)blockIdx.x * kBlock;
+  const uint64_t last = first + kBlock < n_slots ? first + kBlock : n_slots;        // (first < n_slots by the grid)
+  const uint64_t block_base = off[first], block_end = off[last];
+  const uint32_t pad = (uint32_t)(block_base & 3u);
+  const bool staged = STAGE && block_end <= cells_bytes && block_end - block_base + pad <= (uint64_t)kStageBytes;
+  const uint64_t slot = first + threadIdx.x;
+  if (slot < n_slots) {
+    const uint32_t per_line = S.n > 0 ? (uint32_t)S.n : 1u;
+    const uint32_t line = (uint32_t)(slot / per_line), j = (uint32_t)(slot % per_line);
+    uint64_t key = kDroppedKey, tag = 0, src = 0;
+    uint32_t sz = 0;
+    const uint8_t k = kind[slot];
+    if (k != IMP_SLOT_NONE && S.n > 0) {
+      ImpSlot s; s.col = col[slot]; s.end = end[slot]; s.size = size[slot]; s.kind = k; s.err = 0;
+      const uint64_t at = off[slot];
+      // (always true, by the scan: nothing is stored outside the batch's cells, nor outside the block's range of them)
+      if (at >= block_base && at + s.size <= block_end && at + s.size <= cells_bytes && s.size < ((uint64_t)1 << 32)) {
+        const ImpLine L = imp_line_of(B, line);
+        const int64_t row = S.row[j];
+        ImpSink<true> o;
+        o.out = staged ? s_stage + (at - block_base) + pad : cells + at;
+        o.base = at; o.def = def; o.ndef = ndef; o.def_cap = def_cap; o.line = line;
+        const uint32_t e = imp_write(T, L, S.file_idx[j], row, s, o);
+        if (e) imp_raise(err, e, line);
+        key = imp_sort_key(T, s.col, row);
+        src = (uint64_t)(uintptr_t)(cells + at);
+        sz = (uint32_t)s.size;
+        if (k == IMP_SLOT_SPANNING_CANDIDATE) tag = ((uint64_t)s.col << P.seq_bits) | (P.line_seq_base + line + 1u);
+      }
+    }
+    key_out[slot] = key; src_out[slot] = src; size_out[slot] = sz;
+    if (tag_out) tag_out[slot] = tag;
+  }
+  if (!STAGE || !staged) return;      // (uniform over the block)
+  __syncthreads();
+  const uint64_t g0 = block_base - pad;                                   // 4-byte aligned: the cell buffer is
+  const uint32_t n_words = (uint32_t)((block_end - g0 + 3u) >> 2);
+  for (uint32_t w = threadIdx.x; w < n_words; w += kBlock) {
+    const uint64_t g = g0 + 4ull * w;
+    if (g >= block_base && g + 4u <= block_end) *reinterpret_cast<uint32_t*>(cells + g) = *reinterpret_cast<const uint32_t*>(s_stage + 4u * w);
+    else for (uint32_t i = 0; i < 4u; ++i) if (g + i >= block_base && g + i < block_end) cells[g + i] = s_stage[4u * w + i];
+  }
+}
+
+__global__ void k_imp_patch(uint8_t* cells, uint64_t cells_bytes, const uint64_t* at, const uint32_t* value, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || at[i] + 4u > cells_bytes) return;
+  for (int b = 0; b < 4; ++b) cells[at[i] + b] = (uint8_t)(value[i] >> (8 * b));
+}
+
+// a spanning candidate stays only if it is its row's latest cell at or before the partition begin
+__global__ void k_imp_resolve(uint64_t* key, const uint64_t* tag, uint64_t n, const unsigned long long* row_best, int32_t key_row_bits, int64_t max_row,
+                              unsigned long long* counters) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !tag[i] || key[i] == kDroppedKey) return;
+  const int64_t row = (int64_t)(key[i] & (((uint64_t)1 << key_row_bits) - 1u));
+  if (row <= max_row && row_best[row] == tag[i]) atomicAdd(&counters[2], 1ull);
+  else { key[i] = kDroppedKey; atomicAdd(&counters[3], 1ull); }
+}
+
+__global__ void k_imp_iota(uint32_t* v, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) v[i] = (uint32_t)i;
+}
+__global__ void k_imp_sorted_sizes(const uint32_t* idx, const uint32_t* size, uint64_t kept, uint64_t* out /* kept + 1 */) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < kept) out[i] = size[idx[i]];
+  else if (i == kept) out[i] = 0;
+}
+// one wavefront per cell: consecutive lanes copy consecutive bytes
+__global__ void __launch_bounds__(kBlock) k_imp_gather(const uint32_t* idx, const uint64_t* src, const uint32_t* size, const uint64_t* off, uint64_t kept,
+                                                      uint8_t* out, uint64_t out_bytes) {
+  const uint64_t cell = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+  if (cell >= kept) return;
+  const uint32_t lane = threadIdx.x & 63u, slot = idx[cell], n = size[slot];
+  const uint8_t* from = reinterpret_cast<const uint8_t*>((uintptr_t)src[slot]);
+  const uint64_t at = off[cell];
+  if (!from || at + n > out_bytes) return;
+  for (uint32_t i = lane; i < n; i += 64u) out[at + i] = from[i];
+}
+
+template <class T> struct DBuf {       // grow-only device block
+  T* p = nullptr; size_t cap = 0;
+  void ensure(size_t n) {
+    if (n <= cap) return;
+    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    IMP_HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
+    cap = n;
+  }
+  ~DBuf() { if (p) (void)hipFree(p); }
+};
+template <class T> T* dalloc(size_t n) { T* p = nullptr; IMP_HIP_CHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); return p; }
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+}  // namespace
+
+struct DeviceImporter::Impl {
+  int device = 0;
+  ImportOptions opt;
+  uint64_t budget = 0;
+  ImportTablesHost H;
+  std::vector<ImportFile> files;
+  ImportStats st;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // tables, uploaded once
+  DBuf<char> d_names; DBuf<ImpName> d_contigs, d_fields; DBuf<ImpAttr> d_info, d_fmt;
+  DBuf<unsigned long long> d_row_best, d_counters;
+  DBuf<uint32_t> d_err, d_ndef;
+  bool spanning = false; int seq_bits = 64; uint64_t line_seq = 0;
+  bool stage_in_lds = true;          // the A/B of profiles/device_import.md: -7.5 % on the write kernel; GDBAMD_IMPORT_STAGE_LDS=0|1 overrides
+  // per batch, reused
+  DBuf<char> d_text, d_tmp;
+  DBuf<uint64_t> d_tile, d_tile_scan, d_size, d_off, d_patch_at;
+  DBuf<uint32_t> d_nl, d_first_tab, d_tab, d_patch_val;
+  DBuf<int64_t> d_col, d_end, d_samp_row;
+  DBuf<int32_t> d_samp_idx;
+  DBuf<uint8_t> d_kind;
+  DBuf<ImpDeferred> d_def;
+  // what stays until finish()
+  struct Batch { uint64_t n_slots = 0, cells_bytes = 0; uint64_t* key = nullptr; uint64_t* src = nullptr; uint32_t* size = nullptr; uint64_t* tag = nullptr; uint8_t* cells = nullptr; };
+  std::vector<Batch> batches;
+  uint64_t total_slots = 0, total_cells = 0;
+  bool finished = false;
+
+  ImpTables tables(int n_samples) const {
+    ImpTables T = H.view(opt, n_samples);
+    T.names = d_names.p; T.contigs = d_contigs.p; T.fields = d_fields.p; T.info = d_info.p; T.fmt = d_fmt.p;
+    return T;
+  }
+  template <class T> void scan(const T* in, T* out, size_t n) {
+    size_t bytes = 0;
+    IMP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), n, rocprim::plus<T>(), stream));
+    d_tmp.ensure(std::max<size_t>(bytes, 16));
+    IMP_HIP_CHECK(rocprim::exclusive_scan((void*)d_tmp.p, bytes, in, out, T(0), n, rocprim::plus<T>(), stream));
+  }
+  void free_batches() {
+    for (Batch& b : batches) { if (b.key) (void)hipFree(b.key); if (b.src) (void)hipFree(b.src); if (b.size) (void)hipFree(b.size); if (b.tag) (void)hipFree(b.tag); if (b.cells) (void)hipFree(b.cells); }
+    batches.clear();
+  }
+  uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp);   // -> lines of the batch
+};
+
+DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes) : m_(new Impl) {
+  try {
+    m_->device = device;
+    m_->opt = opt;
+    m_->budget = text_budget_bytes ? text_budget_bytes : kDefaultTextBudget;
+    m_->budget = std::min<uint64_t>(m_->budget, (uint64_t)1 << 30);
+    if (const char* e = getenv("GDBAMD_IMPORT_STAGE_LDS")) m_->stage_in_lds = atoi(e) != 0;
+    m_->H = build_import_tables(vid);                 // the refusals: before the device is touched
+    m_->files = import_files(vid, opt);
+    Impl& M = *m_;
+    if (opt.column_begin > 0) {
+      int col_bits = 0;
+      while (col_bits < 63 && (opt.column_begin >> col_bits) != 0) ++col_bits;
+      M.spanning = true;
+      M.seq_bits = 64 - col_bits;
+    }
+    if (DevicePipeline::device_count() <= 0) throw GenomicsDBDeviceException("no HIP device visible: the device importer has no CPU fallback (import_callsets_to_cells is the host importer)");
+    IMP_HIP_CHECK(hipSetDevice(device));
+    IMP_HIP_CHECK(hipStreamCreate(&M.stream));
+    for (auto& e : M.ev) IMP_HIP_CHECK(hipEventCreate(&e));
+    auto up = [&](auto& buf, const auto* src, size_t n) {
+      buf.ensure(std::max<size_t>(n, 1));
+      if (n) IMP_HIP_CHECK(hipMemcpy(buf.p, src, n * sizeof(*src), hipMemcpyHostToDevice));
+    };
+    up(M.d_names, M.H.names.data(), M.H.names.size());
+    up(M.d_contigs, M.H.contigs.data(), M.H.contigs.size());
+    up(M.d_fields, M.H.fields.data(), M.H.fields.size());
+    up(M.d_info, M.H.info.data(), M.H.info.size());
+    up(M.d_fmt, M.H.fmt.data(), M.H.fmt.size());
+    M.d_row_best.ensure((size_t)M.H.max_row + 1);
+    IMP_HIP_CHECK(hipMemset(M.d_row_best.p, 0, ((size_t)M.H.max_row + 1) * sizeof(unsigned long long)));
+    M.d_counters.ensure(4);
+    IMP_HIP_CHECK(hipMemset(M.d_counters.p, 0, 4 * sizeof(unsigned long long)));
+    M.d_err.ensure(kErrWords);
+    M.d_ndef.ensure(1);
+  } catch (...) { this->~DeviceImporter(); throw; }
+}
+
+DeviceImporter::~DeviceImporter() {
+  if (!m_) return;
+  if (m_->stream) { (void)hipSetDevice(m_->device); (void)hipStreamSynchronize(m_->stream); }
+  m_->free_batches();
+  for (auto& e : m_->ev) if (e) (void)hipEventDestroy(e);
+  if (m_->stream) (void)hipStreamDestroy(m_->stream);
+  delete m_;
+  m_ = nullptr;
+}
+
+const ImportStats& DeviceImporter::stats() const { return m_->st; }
+
+void DeviceImporter::import_all() { for (const ImportFile& f : m_->files) append_file(f.name); }
+
+void DeviceImporter::append_file(const std::string& filename) {
+  Impl& M = *m_;
+  IMP_HIP_CHECK(hipSetDevice(M.device));
+  const ImportFile* file = nullptr;
+  for (const ImportFile& f : M.files) if (f.name == filename) file = &f;
+  if (!file) throw VCF2BinaryException("file " + filename + " is not in the callset mapping");
+  const double t0 = now_s();
+  std::string text;
+  try { text = gz_text::read_all(file->path); }
+  catch (const std::exception&) { throw VCF2BinaryException("cannot open " + file->path); }
+  M.st.s_read += now_s() - t0;
+  ++M.st.num_files;
+  const ImportHeader hdr = parse_import_header(text, *file);
+  std::vector<int32_t> samp_idx;
+  std::vector<int64_t> samp_row;
+  for (int s = 0; s < hdr.n_samples; ++s) if (hdr.sample_row[(size_t)s] >= 0) { samp_idx.push_back(s); samp_row.push_back(hdr.sample_row[(size_t)s]); }
+  const int n_imp = (int)samp_idx.size();
+  M.d_samp_idx.ensure(std::max(n_imp, 1));
+  M.d_samp_row.ensure(std::max(n_imp, 1));
+  if (n_imp) {
+    IMP_HIP_CHECK(hipMemcpyAsync(M.d_samp_idx.p, samp_idx.data(), (size_t)n_imp * sizeof(int32_t), hipMemcpyHostToDevice, M.stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(M.d_samp_row.p, samp_row.data(), (size_t)n_imp * sizeof(int64_t), hipMemcpyHostToDevice, M.stream));
+    IMP_HIP_CHECK(hipStreamSynchronize(M.stream));
+  }
+  // batches of at most the budget, cut behind a newline; a line longer than the budget grows its batch
+  size_t pos = hdr.record_begin;
+  int64_t lines_before = hdr.lines_before;
+  while (pos < text.size()) {
+    size_t stop = text.size();
+    if (stop - pos > M.budget) {
+      const void* nl = memrchr(text.data() + pos, '\n', (size_t)M.budget);
+      if (!nl) nl = memchr(text.data() + pos + M.budget, '\n', text.size() - pos - (size_t)M.budget);
+      if (nl) stop = (size_t)((const char*)nl - text.data()) + 1;
+    }
+    const size_t n = stop - pos;
+    if (n >= ((size_t)1 << 31)) throw VCF2BinaryException("a record line of 2 GiB or more in " + file->path);
+    const bool add_newline = text[stop - 1] != '\n';
+    lines_before += M.batch(*file, hdr, text.data() + pos, n, add_newline, lines_before, n_imp);
+    pos = stop;
+  }
+}
+
+uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n_text, bool add_newline, int64_t lines_before, int n_imp) {
+  const uint32_t n = (uint32_t)(n_text + (add_newline ? 1 : 0));
+  ++st.num_batches;
+  st.text_bytes += n_text;
+  double t0 = now_s();
+  d_text.ensure((size_t)n + kTextPad);
+  IMP_HIP_CHECK(hipMemcpyAsync(d_text.p, text, n_text, hipMemcpyHostToDevice, stream));
+  if (add_newline) IMP_HIP_CHECK(hipMemsetAsync(d_text.p + n_text, '\n', 1, stream));
+  IMP_HIP_CHECK(hipMemsetAsync(d_text.p + n, 0, kTextPad, stream));
+  IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  st.s_h2d += now_s() - t0;
+
+  // ---- index
+  const uint32_t n_tiles = (n + kTile - 1u) / kTile;
+  d_tile.ensure((size_t)n_tiles + 1);
+  d_tile_scan.ensure((size_t)n_tiles + 1);
+  IMP_HIP_CHECK(hipEventRecord(ev[0], stream));
+  IMP_HIP_CHECK(hipMemsetAsync(d_tile.p + n_tiles, 0, sizeof(uint64_t), stream));
+  hipLaunchKernelGGL(k_imp_count, dim3(n_tiles), dim3(kBlock), 0, stream, (const char*)d_text.p, n, d_tile.p);
+  scan<uint64_t>(d_tile.p, d_tile_scan.p, (size_t)n_tiles + 1);
+  uint64_t totals = 0;
+  IMP_HIP_CHECK(hipMemcpyAsync(&totals, d_tile_scan.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  const uint32_t n_lines = (uint32_t)(totals >> 32), n_tabs = (uint32_t)totals;     // (the text ends with a newline)
+  if (n_lines == 0) return 0;
+  d_nl.ensure(n_lines);
+  d_first_tab.ensure((size_t)n_lines + 1);
+  d_tab.ensure(std::max<uint32_t>(n_tabs, 1));
+  IMP_HIP_CHECK(hipMemsetAsync(d_first_tab.p, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(k_imp_scatter, dim3(n_tiles), dim3(kBlock), 0, stream, (const char*)d_text.p, n, (const uint64_t*)d_tile_scan.p, d_nl.p, d_first_tab.p, d_tab.p,
+                     n_lines, n_tabs);
+  IMP_HIP_CHECK(hipEventRecord(ev[1], stream));
+
+  // ---- measure
+  if (spanning && seq_bits < 64 && ((line_seq + n_lines + 1) >> seq_bits) != 0)
+    throw VCF2BinaryException("too many record lines for the partition-begin rule of the device importer at column_begin " + std::to_string(opt.column_begin));
+  const uint64_t n_slots = (uint64_t)n_lines * (uint64_t)std::max(n_imp, 1);
+  if (total_slots + n_slots >= ((uint64_t)1 << 32)) throw VCF2BinaryException("more than 2^32 (record line, sample) pairs in one device import: split the callset mapping");
+  d_col.ensure(n_slots); d_end.ensure(n_slots); d_size.ensure(n_slots + 1); d_off.ensure(n_slots + 1); d_kind.ensure(n_slots);
+  const ImpTables T = tables(hdr.n_samples);
+  const ImpBatch B{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines};
+  const ImpSamples S{d_samp_idx.p, d_samp_row.p, n_imp};
+  const ImpSpan P{spanning ? d_row_best.p : nullptr, seq_bits, line_seq, H.max_row};
+  IMP_HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(uint32_t), stream));
+  IMP_HIP_CHECK(hipMemsetAsync(d_err.p + 1, 0xFF, (kErrWords - 1) * sizeof(uint32_t), stream));
+  IMP_HIP_CHECK(hipMemsetAsync(d_counters.p, 0, 2 * sizeof(unsigned long long), stream));
+  IMP_HIP_CHECK(hipMemsetAsync(d_size.p + n_slots, 0, sizeof(uint64_t), stream));
+  hipLaunchKernelGGL(k_imp_measure, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, B, S, P, n_slots, d_col.p, d_end.p, d_size.p, d_kind.p, d_err.p, d_counters.p);
+  IMP_HIP_CHECK(hipEventRecord(ev[2], stream));
+  scan<uint64_t>(d_size.p, d_off.p, (size_t)n_slots + 1);
+  uint64_t cells_bytes = 0;
+  unsigned long long counters[2] = {0, 0};
+  IMP_HIP_CHECK(hipMemcpyAsync(&cells_bytes, d_off.p + n_slots, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  IMP_HIP_CHECK(hipMemcpyAsync(counters, d_counters.p, sizeof(counters), hipMemcpyDeviceToHost, stream));
+  IMP_HIP_CHECK(hipStreamSynchronize(stream));
+
+  // ---- write
+  batches.emplace_back();
+  Batch& b = batches.back();
+  b.n_slots = n_slots; b.cells_bytes = cells_bytes;
+  b.key = dalloc<uint64_t>(n_slots); b.src = dalloc<uint64_t>(n_slots); b.size = dalloc<uint32_t>(n_slots);
+  if (spanning) b.tag = dalloc<uint64_t>(n_slots);
+  b.cells = dalloc<uint8_t>(cells_bytes + 16);
+  d_def.ensure(std::max<size_t>(d_def.cap, 1 << 16));
+  uint32_t ndef = 0;
+  uint32_t err[kErrWords];
+  for (int attempt = 0;; ++attempt) {
+    IMP_HIP_CHECK(hipMemsetAsync(d_ndef.p, 0, sizeof(uint32_t), stream));
+    IMP_HIP_CHECK(hipEventRecord(ev[3], stream));
+    if (stage_in_lds)
+      hipLaunchKernelGGL(k_imp_write<true>, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, B, S, P, n_slots, (const int64_t*)d_col.p, (const int64_t*)d_end.p,
+                         (const uint64_t*)d_size.p, (const uint8_t*)d_kind.p, (const uint64_t*)d_off.p, b.cells, cells_bytes, d_def.p, d_ndef.p, (uint32_t)d_def.cap,
+                         b.key, b.src, b.size, b.tag, d_err.p);
+    else
+      hipLaunchKernelGGL(k_imp_write<false>, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, B, S, P, n_slots, (const int64_t*)d_col.p, (const int64_t*)d_end.p,
+                         (const uint64_t*)d_size.p, (const uint8_t*)d_kind.p, (const uint64_t*)d_off.p, b.cells, cells_bytes, d_def.p, d_ndef.p, (uint32_t)d_def.cap,
+                         b.key, b.src, b.size, b.tag, d_err.p);
+    IMP_HIP_CHECK(hipEventRecord(ev[4], stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(&ndef, d_ndef.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, stream));
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
+    if (ndef <= d_def.cap || attempt > 0) break;
+    d_def.ensure(ndef);            // the list was too short: the write pass is repeated into the same places
+  }
+  if (ndef > d_def.cap) throw GenomicsDBDeviceException("deferred-token list overflow");
+  float ms = 0;
+  IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1])); st.ms_index += ms;
+  IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[1], ev[2])); st.ms_measure += ms;
+  IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[3], ev[4])); st.ms_write += ms;
+
+  // ---- deferred tokens: the host importer's parsers, on exactly those tokens
+  t0 = now_s();
+  std::vector<ImpDeferred> def(ndef);
+  if (ndef) IMP_HIP_CHECK(hipMemcpy(def.data(), d_def.p, (size_t)ndef * sizeof(ImpDeferred), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> patch_at(ndef);
+  std::vector<uint32_t> patch_val(ndef);
+  uint32_t bad_line = UINT32_MAX;
+  std::string bad_text;
+  for (uint32_t i = 0; i < ndef; ++i) {
+    const ImpDeferred& d = def[i];
+    if ((uint64_t)d.tok_off + d.tok_len > n_text) throw GenomicsDBDeviceException("deferred token outside the batch");
+    patch_at[i] = d.out_off;
+    try { patch_val[i] = resolve_deferred(d, text, H); }
+    catch (const VCF2BinaryException& e) {
+      if (d.line < bad_line) { bad_line = d.line; bad_text = e.what(); bad_text = bad_text.substr(strlen("VCF2BinaryException : ")); }
+    }
+  }
+  // ---- errors: the smallest offending line speaks
+  uint32_t err_line = UINT32_MAX, err_bit = 0;
+  for (int k = 0; k < kErrWords - 1; ++k) if ((err[0] & (1u << k)) && err[1 + k] < err_line) { err_line = err[1 + k]; err_bit = 1u << k; }
+  if (err_bit || bad_line != UINT32_MAX) {
+    const uint32_t line = std::min(err_line, bad_line);
+    const std::string where = file.path + " line " + std::to_string(lines_before + (int64_t)line + 1);
+    if (err_line <= bad_line) {
+      uint32_t lb = 0, le = 0;
+      if (line) { IMP_HIP_CHECK(hipMemcpy(&lb, d_nl.p + (line - 1), sizeof(uint32_t), hipMemcpyDeviceToHost)); ++lb; }
+      IMP_HIP_CHECK(hipMemcpy(&le, d_nl.p + line, sizeof(uint32_t), hipMemcpyDeviceToHost));
+      le = std::min<uint32_t>(le, (uint32_t)n_text);
+      throw VCF2BinaryException(describe_line_error(err_bit, H, opt, hdr, text, lb, le, where));
+    }
+    throw VCF2BinaryException(bad_text + " (" + where + ")");
+  }
+  if (ndef) {
+    d_patch_at.ensure(ndef); d_patch_val.ensure(ndef);
+    IMP_HIP_CHECK(hipMemcpyAsync(d_patch_at.p, patch_at.data(), (size_t)ndef * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(d_patch_val.p, patch_val.data(), (size_t)ndef * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_imp_patch, dim3(grid_for(ndef)), dim3(kBlock), 0, stream, b.cells, cells_bytes, (const uint64_t*)d_patch_at.p, (const uint32_t*)d_patch_val.p, ndef);
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  st.s_deferred += now_s() - t0;
+  st.num_deferred_values += ndef;
+  st.num_records += (int64_t)counters[0];
+  total_cells += counters[1];
+  total_slots += n_slots;
+  line_seq += n_lines;
+  return n_lines;
+}
+
+void DeviceImporter::finish(std::vector<uint8_t>& cells) {
+  Impl& M = *m_;
+  IMP_HIP_CHECK(hipSetDevice(M.device));
+  if (M.finished) throw VCF2BinaryException("DeviceImporter::finish called twice");
+  M.finished = true;
+  cells.clear();
+  const uint64_t N = M.total_slots;
+  if (N == 0 || M.total_cells == 0) { M.st.num_cells = 0; M.st.num_bytes = 0; M.free_batches(); return; }
+  hipStream_t st = M.stream;
+  DBuf<uint64_t> key, key_sorted, src, tag, sorted_size, sorted_off;
+  DBuf<uint32_t> size, idx, idx_sorted;
+  key.ensure(N); key_sorted.ensure(N); src.ensure(N); size.ensure(N); idx.ensure(N); idx_sorted.ensure(N);
+  if (M.spanning) tag.ensure(N);
+  IMP_HIP_CHECK(hipEventRecord(M.ev[0], st));
+  uint64_t at = 0;
+  for (const Impl::Batch& b : M.batches) {
+    IMP_HIP_CHECK(hipMemcpyAsync(key.p + at, b.key, b.n_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    IMP_HIP_CHECK(hipMemcpyAsync(src.p + at, b.src, b.n_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    IMP_HIP_CHECK(hipMemcpyAsync(size.p + at, b.size, b.n_slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (M.spanning) IMP_HIP_CHECK(hipMemcpyAsync(tag.p + at, b.tag, b.n_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    at += b.n_slots;
+  }
+  IMP_HIP_CHECK(hipMemsetAsync(M.d_counters.p, 0, 4 * sizeof(unsigned long long), st));
+  if (M.spanning)
+    hipLaunchKernelGGL(k_imp_resolve, dim3(grid_for(N)), dim3(kBlock), 0, st, key.p, (const uint64_t*)tag.p, N, (const unsigned long long*)M.d_row_best.p, M.H.key_row_bits,
+                       M.H.max_row, M.d_counters.p);
+  hipLaunchKernelGGL(k_imp_iota, dim3(grid_for(N)), dim3(kBlock), 0, st, idx.p, N);
+  {
+    size_t bytes = 0;
+    IMP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key_sorted.p, idx.p, idx_sorted.p, (size_t)N, 0, 64, st));
+    M.d_tmp.ensure(std::max<size_t>(bytes, 16));
+    IMP_HIP_CHECK(rocprim::radix_sort_pairs((void*)M.d_tmp.p, bytes, key.p, key_sorted.p, idx.p, idx_sorted.p, (size_t)N, 0, 64, st));
+  }
+  unsigned long long counters[4] = {0, 0, 0, 0};
+  IMP_HIP_CHECK(hipMemcpyAsync(counters, M.d_counters.p, sizeof(counters), hipMemcpyDeviceToHost, st));
+  IMP_HIP_CHECK(hipStreamSynchronize(st));
+  const uint64_t kept = M.total_cells - counters[3];       // the dropped keys sort behind every cell
+  M.st.num_spanning_cells = (int64_t)counters[2];
+  M.st.num_cells = (int64_t)kept;
+  uint64_t out_bytes = 0;
+  DBuf<uint8_t> out;
+  if (kept) {
+    sorted_size.ensure(kept + 1); sorted_off.ensure(kept + 1);
+    hipLaunchKernelGGL(k_imp_sorted_sizes, dim3(grid_for(kept + 1)), dim3(kBlock), 0, st, (const uint32_t*)idx_sorted.p, (const uint32_t*)size.p, kept, sorted_size.p);
+    M.scan<uint64_t>(sorted_size.p, sorted_off.p, (size_t)kept + 1);
+    IMP_HIP_CHECK(hipMemcpyAsync(&out_bytes, sorted_off.p + kept, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    IMP_HIP_CHECK(hipStreamSynchronize(st));
+    out.ensure(out_bytes + 16);
+    hipLaunchKernelGGL(k_imp_gather, dim3(grid_for(kept * 64)), dim3(kBlock), 0, st, (const uint32_t*)idx_sorted.p, (const uint64_t*)src.p, (const uint32_t*)size.p,
+                       (const uint64_t*)sorted_off.p, kept, out.p, out_bytes);
+  }
+  IMP_HIP_CHECK(hipEventRecord(M.ev[1], st));
+  IMP_HIP_CHECK(hipStreamSynchronize(st));
+  float ms = 0;
+  IMP_HIP_CHECK(hipEventElapsedTime(&ms, M.ev[0], M.ev[1]));
+  M.st.ms_sort_gather += ms;
+  const double t0 = now_s();
+  cells.resize(out_bytes);
+  if (out_bytes) IMP_HIP_CHECK(hipMemcpy(cells.data(), out.p, out_bytes, hipMemcpyDeviceToHost));
+  M.st.s_d2h += now_s() - t0;
+  M.st.num_bytes = out_bytes;
+  M.free_batches();
+}
+
+std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes, ImportStats* stats) {
+  const double t0 = now_s();
+  DeviceImporter imp(device, vid, opt, text_budget_bytes);
+  imp.import_all();
+  std::vector<uint8_t> out;
+  imp.finish(out);
+  if (stats) { *stats = imp.stats(); stats->s_total = now_s() - t0; }
+  return out;
+}
+
+}  // namespace genomicsdb_amd

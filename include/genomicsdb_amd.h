@@ -248,6 +248,17 @@ int gdbamd_column_partition(const char* loader_json_text, int rank, int64_t* beg
  * "filename" entries (NULL / "": as they are).  *cells is malloc'ed: release with gdbamd_free.  0 on success. */
 int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                         int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells);
+/* The same import with the conversion on GPU `device` (kernels/gdb_import.hip): byte for byte the cells of gdbamd_import_cells.
+ * The host reads and inflates the files; the device indexes, measures, writes, sorts and gathers.  text_budget_bytes: record text
+ * per batch (0: default).  Numeric tokens outside the device's exact fast path are parsed by the host importer's functions
+ * (stats slot 5 counts them).  Refused with an error that names the field: 2-dimensional (allele-specific) fields and flattened
+ * tuple elements - gdbamd_import_cells serves those vids.  stats: NULL or GDBAMD_IMPORT_NUM_STATS doubles:
+ *   0 files, 1 records, 2 cells, 3 spanning cells, 4 bytes, 5 deferred values, 6 batches, 7 text bytes,
+ *   8..11 HIP-event ms of index / measure / write / sort + gather, 12..16 wall seconds of file read, H2D, deferred parse, D2H, total */
+#define GDBAMD_IMPORT_NUM_STATS 17
+int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                               int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
+                               double* stats);
 void gdbamd_free(void* p);
 
 #ifdef __cplusplus
