@@ -355,15 +355,22 @@ def unpin_host_memory(addr):
 
 
 IMPORT_STAT_NAMES = ("num_files", "num_records", "num_cells", "num_spanning_cells", "num_bytes", "num_deferred_values", "num_batches", "text_bytes",
-                     "ms_index", "ms_measure", "ms_write", "ms_sort_gather", "s_read", "s_h2d", "s_deferred", "s_d2h", "s_total")
+                     "ms_index", "ms_measure", "ms_write", "ms_sort_gather", "s_read", "s_h2d", "s_deferred", "s_d2h", "s_total",
+                     "compressed_bytes", "num_device_members", "num_host_inflated_files", "ms_inflate", "bytes_h2d")
+INFLATE_MODES = {"auto": 0, "host": 1, "device": 2}
 
 
 def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_deletions_as_intervals=True, column_begin=0, column_end=2**63 - 2,
-                 device=None, text_budget_bytes=0, stats=None):
+                 device=None, text_budget_bytes=0, stats=None, inflate="auto"):
     """(g)VCFs of a callset mapping -> begin-cells (bytes, reference binary cell layout, column-major) of one column partition:
     the conversion step of the reference's vcf2tiledb (vcf2binary.cc:991-1196).
     device=None: host code, no device needed.  device=<int>: the conversion runs on that GPU (kernels/gdb_import.hip) and gives
-    the same bytes; text_budget_bytes is the record text per batch (0: default) and `stats`, a dict, receives IMPORT_STAT_NAMES."""
+    the same bytes; text_budget_bytes is the record text per batch (0: default) and `stats`, a dict, receives IMPORT_STAT_NAMES.
+    inflate (device path only): "auto" - bgzip'ed (BGZF) files cross the link compressed and are inflated on the device
+    (kernels/gdb_inflate.hip), every other file goes through zlib on the host; "host" - zlib for every file; "device" - a file that
+    is not BGZF is an error.  A BGZF member with a bad stream, ISIZE or CRC32 refuses the import."""
+    if inflate not in INFLATE_MODES:
+        raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
     L = _lib.lib()
     p = ctypes.c_void_p()
     n = ctypes.c_uint64()
@@ -373,9 +380,9 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
                                    column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc))
     else:
         st = (ctypes.c_double * len(IMPORT_STAT_NAMES))()
-        rc = L.gdbamd_import_cells_device(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
-                                          1 if treat_deletions_as_intervals else 0, column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc),
-                                          int(device), int(text_budget_bytes), st)
+        rc = L.gdbamd_import_cells_device_ex(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
+                                             1 if treat_deletions_as_intervals else 0, column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc),
+                                             int(device), int(text_budget_bytes), INFLATE_MODES[inflate], st, len(IMPORT_STAT_NAMES))
         if rc == 0 and stats is not None:
             stats.update({k: (float(v) if k[:2] in ("ms", "s_") else int(v)) for k, v in zip(IMPORT_STAT_NAMES, st)})
     _check(rc == 0, "import_cells")
@@ -395,6 +402,19 @@ def bgzf_compress(data, vcf_text=False):
     n = ctypes.c_uint64()
     ms = ctypes.c_float()
     _check(L.gdbamd_bgzf_compress_mode(data, len(data), dst, cap, ctypes.byref(n), ctypes.byref(ms), 1 if vcf_text else 0) == 0, "bgzf_compress")
+    return dst.raw[:n.value], ms.value
+
+
+def bgzf_decompress(data, device=0):
+    """the bytes of a whole BGZF buffer, inflated and verified (stream, ISIZE, CRC32 per member) by the device kernel of
+    kernels/gdb_inflate.hip; returns (bytes, kernel ms).  A bad member raises an error that names its byte offset."""
+    L = _lib.lib()
+    data = bytes(data)
+    n = ctypes.c_uint64()
+    ms = ctypes.c_float()
+    _check(L.gdbamd_bgzf_decompress(data, len(data), None, 0, ctypes.byref(n), None, int(device)) == 0, "bgzf_decompress")
+    dst = ctypes.create_string_buffer(max(n.value, 1))
+    _check(L.gdbamd_bgzf_decompress(data, len(data), dst, n.value, ctypes.byref(n), ctypes.byref(ms), int(device)) == 0, "bgzf_decompress")
     return dst.raw[:n.value], ms.value
 
 

@@ -19,6 +19,7 @@ SOURCES = [
     "kernels/gdb_pipeline.hip",
     "kernels/gdb_bgzf.hip",
     "kernels/gdb_import.hip",
+    "kernels/gdb_inflate.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -120,6 +121,12 @@ def build_hostsim_import():
     """CPU harness around the bodies of the device importer (core/gdb_import.hpp; tests only)"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_import")])
     return os.path.join(ROOT, "tests", "hostsim_import", "libhostsim_import.so")
+
+
+def build_hostsim_inflate():
+    """CPU harness around the bodies of the BGZF inflater (core/gdb_inflate.hpp; tests only)"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_inflate")])
+    return os.path.join(ROOT, "tests", "hostsim_inflate", "libhostsim_inflate.so")
 
 
 if __name__ == "__main__":

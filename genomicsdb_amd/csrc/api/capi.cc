@@ -9,6 +9,7 @@
 
 #include "genomicsdb_bcf_generator.h"
 #include "../kernels/gdb_bgzf.h"
+#include "../kernels/gdb_inflate.h"
 #include "../host/vcf_importer.h"
 #include "../host/vcf_index.h"
 
@@ -140,6 +141,38 @@ int gdbamd_bgzf_compress_mode(const uint8_t* src, uint64_t n, uint8_t* dst, uint
   }, -1);
 }
 uint64_t gdbamd_bgzf_bound(uint64_t n) { return bgzf_bound(n); }
+// the counterpart: a whole BGZF buffer inflated by the kernel of kernels/gdb_inflate.hip (a utility and its test hook)
+int gdbamd_bgzf_decompress(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* dst_len, float* ms_kernels, int device) {
+  return guarded([&]() -> int {
+    if (!src || !dst_len) throw GenomicsDBConfigException("gdbamd_bgzf_decompress: null argument");
+    std::vector<BgzfMember> mem;
+    uint64_t total = 0;
+    uint64_t break_at = 0;
+    if (!bgzf_walk(src, n, mem, &total, &break_at))
+      throw GenomicsDBConfigException("gdbamd_bgzf_decompress: the buffer is not BGZF from its first byte to its last: no whole member at byte offset " + std::to_string(break_at));
+    *dst_len = total;
+    if (!dst) return 0;
+    if (total > dst_cap) throw GenomicsDBDeviceException("destination too small: " + std::to_string(total) + " bytes needed");
+    if (DevicePipeline::device_count() <= 0) throw GenomicsDBDeviceException("no HIP device visible");
+    if (hipSetDevice(device) != hipSuccess) throw GenomicsDBDeviceException("no HIP device " + std::to_string(device));
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, (size_t)total + 64) != hipSuccess) throw GenomicsDBDeviceException("hipMalloc failed");
+    try {
+      BgzfDeviceInflater inf;
+      const size_t step = 8192;           // members per launch: at most 512 MiB of them
+      for (size_t m0 = 0; m0 < mem.size(); m0 += step) {
+        const size_t m1 = std::min(mem.size(), m0 + step);
+        uint32_t err = 0;
+        const int64_t bad = inf.inflate(src, mem.data(), m0, m1, d + mem[m0].out_off, nullptr, &err);
+        if (bad >= 0) throw GenomicsDBDeviceException("corrupt BGZF member at byte offset " + std::to_string(mem[(size_t)bad].offset) + ": " + bgzf_inflate_error_text(err));
+      }
+      if (ms_kernels) *ms_kernels = inf.ms_kernel;
+      if (total && hipMemcpy(dst, d, (size_t)total, hipMemcpyDeviceToHost) != hipSuccess) throw GenomicsDBDeviceException("copy from the device failed");
+    } catch (...) { (void)hipFree(d); throw; }
+    (void)hipFree(d);
+    return 0;
+  }, -1);
+}
 void gdbamd_engine_destroy(void* e) { delete (EngineHandle*)e; }
 int gdbamd_engine_num_fields(void* e) { return e ? ((EngineHandle*)e)->eng->plan().plan.nfields : -1; }
 const char* gdbamd_engine_field_name(void* e, int f) {
@@ -420,6 +453,12 @@ int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mappin
 int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                                int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
                                double* stats) {
+  return gdbamd_import_cells_device_ex(vid_mapping_file, callset_mapping_file, file_root, treat_deletions_as_intervals, column_begin, column_end, cells, nbytes, ncells,
+                                       device, text_budget_bytes, 0, stats, stats ? GDBAMD_IMPORT_NUM_STATS : 0);
+}
+int gdbamd_import_cells_device_ex(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                                  int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
+                                  int inflate_mode, double* stats, int nstats) {
   try {
     if (!vid_mapping_file || !callset_mapping_file || !cells || !nbytes) throw GenomicsDBConfigException("gdbamd_import_cells_device: null argument");
     VidMapper vid;
@@ -431,17 +470,18 @@ int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset
     opt.column_end = column_end;
     if (file_root) opt.file_root = file_root;
     ImportStats st;
-    const std::vector<uint8_t> out = import_callsets_to_cells_device(vid, opt, device, text_budget_bytes, &st);
+    const std::vector<uint8_t> out = import_callsets_to_cells_device(vid, opt, device, text_budget_bytes, &st, inflate_mode);
     *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
     if (!*cells) throw GenomicsDBConfigException("out of memory");
     if (!out.empty()) memcpy(*cells, out.data(), out.size());
     *nbytes = out.size();
     if (ncells) *ncells = st.num_cells;
-    if (stats) {
-      const double v[GDBAMD_IMPORT_NUM_STATS] = {(double)st.num_files, (double)st.num_records, (double)st.num_cells, (double)st.num_spanning_cells, (double)st.num_bytes,
-                                                 (double)st.num_deferred_values, (double)st.num_batches, (double)st.text_bytes, st.ms_index, st.ms_measure, st.ms_write,
-                                                 st.ms_sort_gather, st.s_read, st.s_h2d, st.s_deferred, st.s_d2h, st.s_total};
-      memcpy(stats, v, sizeof(v));
+    if (stats && nstats > 0) {
+      const double v[GDBAMD_IMPORT_NUM_STATS_EX] = {(double)st.num_files, (double)st.num_records, (double)st.num_cells, (double)st.num_spanning_cells, (double)st.num_bytes,
+                                                    (double)st.num_deferred_values, (double)st.num_batches, (double)st.text_bytes, st.ms_index, st.ms_measure, st.ms_write,
+                                                    st.ms_sort_gather, st.s_read, st.s_h2d, st.s_deferred, st.s_d2h, st.s_total,
+                                                    (double)st.compressed_bytes, (double)st.num_device_members, (double)st.num_host_inflated_files, st.ms_inflate, (double)st.bytes_h2d};
+      memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_IMPORT_NUM_STATS_EX));
     }
     g_last_error.clear();
     return 0;

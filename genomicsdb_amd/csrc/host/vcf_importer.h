@@ -42,16 +42,24 @@ struct ImportStats {
   int64_t num_batches = 0; uint64_t text_bytes = 0;
   float ms_index = 0, ms_measure = 0, ms_write = 0, ms_sort_gather = 0;      // HIP-event time per phase, summed over the batches
   double s_read = 0, s_h2d = 0, s_deferred = 0, s_d2h = 0, s_total = 0;     // wall clock: file read + inflate, text upload, host parsing of deferred tokens, result download
+  // BGZF input of the device path (kernels/gdb_inflate.hip)
+  uint64_t compressed_bytes = 0;       // bytes of the input files as they are on disk
+  int64_t num_device_members = 0;      // BGZF members inflated on the device
+  int64_t num_host_inflated_files = 0; // files inflated whole on the host (not BGZF, or inflate_mode = host)
+  float ms_inflate = 0;                // HIP-event time of the inflate kernel
+  uint64_t bytes_h2d = 0;              // input bytes uploaded: text (host inflate) or compressed members, their descriptors and the header member's tail
 };
 
 // every callset of vid's callset mapping (file, idx_in_file, row_idx); cells in column-major (column, row) order
 std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const ImportOptions& opt, ImportStats* stats = nullptr);
 
-// The same bytes, made on GPU `device` (kernels/gdb_import.hip): the host reads and inflates the files and maps the samples,
-// the device indexes, measures, writes, sorts and gathers the cells.  text_budget_bytes: record text per batch (0: default).
-// Refuses, before any launch, 2-dimensional fields, flattened tuple elements and what import_callsets_to_cells refuses.
+// The same bytes, made on GPU `device` (kernels/gdb_import.hip): the host reads the files and maps the samples, the device
+// inflates BGZF input, indexes, measures, writes, sorts and gathers the cells.  text_budget_bytes: record text per batch (0: default).
+// inflate_mode: 0 BGZF files are inflated on the device and every other file on the host, 1 always on the host, 2 a file that is
+// not BGZF is an error.  Refuses, before any launch, 2-dimensional fields, flattened tuple elements and what
+// import_callsets_to_cells refuses; a BGZF member whose stream, ISIZE or CRC32 is wrong refuses the file.
 std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes,
-                                                     ImportStats* stats = nullptr);
+                                                     ImportStats* stats = nullptr, int inflate_mode = 0);
 
 // the importer's number parsers (strtoll / strtod over the whole token, VCF2BinaryException otherwise): the device path runs
 // them on the tokens it deferred

@@ -1,7 +1,9 @@
 // gdb_import.h - the device importer: (g)VCF record text -> begin-cells on one GPU (host-visible interface, no HIP types).
 //
-// The host reads and inflates a file, maps its samples to rows from the #CHROM line and hands the record text over in batches of at
-// most `text_budget_bytes`, cut at a newline.  Per batch the device indexes newlines and tabs, measures one cell per
+// The host reads a file, maps its samples to rows from the #CHROM line and hands the record text over in batches of at most
+// `text_budget_bytes`, cut at a newline.  A BGZF file crosses the link compressed: only the members that hold the header are
+// inflated on the host, the rest on the device (kernels/gdb_inflate.hip), in windows of about one text budget; every other file is
+// inflated on the host and its text uploaded.  Per batch the device indexes newlines and tabs, measures one cell per
 // (record line, imported sample), lays the cells out by a scan and writes them - the bodies of core/gdb_import.hpp, the same
 // bytes as host/vcf_importer.cc.  finish() resolves the intervals that span the partition begin, sorts all cells by
 // (column, row) with ties in append order, gathers them into column-major order and copies the result out once.
@@ -19,7 +21,8 @@ class DeviceImporter {
  public:
   static constexpr uint64_t kDefaultTextBudget = (uint64_t)64 << 20;
   // refuses (VCF2BinaryException) what the bodies do not cover before anything is launched
-  DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes = 0);
+  enum { kInflateAuto = 0, kInflateHost = 1, kInflateDevice = 2 };      // BGZF on the device else the host; always the host; a file that is not BGZF is an error
+  DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes = 0, int inflate_mode = kInflateAuto);
   ~DeviceImporter();
   DeviceImporter(const DeviceImporter&) = delete;
   DeviceImporter& operator=(const DeviceImporter&) = delete;

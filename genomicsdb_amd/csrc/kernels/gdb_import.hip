@@ -10,9 +10,21 @@
 // finish():  k_imp_resolve drops the spanning candidates that are not their row's choice, a stable rocPRIM radix sort of the keys
 //            over the slots of all batches (slots are in the host importer's append order, so ties resolve as std::stable_sort
 //            does), k_imp_gather copies the variable-size cells into column-major order, one copy to the host.
+//
+// Where the text comes from: a BGZF file (a valid chain of members from its first byte to its last, bgzf_walk) is read as it is; the
+// host inflates only the leading members that hold the '#' lines, the rest goes to the device in WINDOWS of whole members
+// (kernels/gdb_inflate.hip: one wavefront per member; stream, ISIZE and CRC32 of every member verified).  A window is [the
+// partial line carried from the window before | the inflated members], about one text budget, floor one member; batches are cut
+// inside it exactly as on the host - the last newline below the budget is found by k_imp_find_newlines - and copied, device to
+// device, to the aligned and padded d_text the kernels above read.  The bytes behind a window's last newline are carried to the
+// front of the next one, so a batch never crosses a window: with the same budget, num_batches can be larger than for the same text
+// inflated on the host (the cells do not depend on where batches are cut), and each cut costs one small launch and round trip.  Every other file (plain text, plain gzip, a chain that breaks) is inflated by gz_text::read_all and
+// its text uploaded, as before.
 #include "gdb_import.h"
 
 #include <hip/hip_runtime.h>
+#include <sys/stat.h>
+#include <zlib.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -20,9 +32,11 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 
 #include "../common/gz_text.hpp"
 #include "../host/import_common.hpp"
+#include "gdb_inflate.h"
 #include "gdb_pipeline.h"
 
 namespace genomicsdb_amd {
@@ -96,6 +110,24 @@ __global__ void __launch_bounds__(kBlock) k_imp_scatter(const char* text, uint32
     if (b[i] == '\n') { if (nl < n_lines) { nl_pos[nl] = (uint32_t)at + i; line_first_tab[nl + 1u] = tab; } ++nl; }
     else if (b[i] == '\t') { if (tab < n_tabs) tab_pos[tab] = (uint32_t)at + i; ++tab; }
   }
+}
+
+// where a batch is cut: out[0] = 1 + position of the last newline in [lo, mid) (0: none), out[1] = position of the first newline in
+// [mid, hi) (all ones: none); one thread per byte of [lo, hi), one atomic per wavefront and side
+__global__ void __launch_bounds__(kBlock) k_imp_find_newlines(const char* text, uint64_t lo, uint64_t mid, uint64_t hi, unsigned long long* out) {
+  const uint64_t i = lo + (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool nl = i < hi && text[i] == '\n';
+  const bool below = nl && i < mid, above = nl && i >= mid;
+  const unsigned long long b = __ballot(below), a = __ballot(above);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (below && lane == 63u - (uint32_t)__clzll((long long)b)) atomicMax(&out[0], (unsigned long long)i + 1ull);
+  if (above && lane == (uint32_t)__ffsll((unsigned long long)a) - 1u) atomicMin(&out[1], (unsigned long long)i);
+}
+// a line that begins with "#CHROM" (the caller's text begins at a line start)
+__global__ void __launch_bounds__(kBlock) k_imp_find_chrom(const char* text, uint64_t n, uint32_t* found) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i + 6u > n || text[i] != '#' || (i > 0 && text[i - 1u] != '\n')) return;
+  if (text[i + 1u] == 'C' && text[i + 2u] == 'H' && text[i + 3u] == 'R' && text[i + 4u] == 'O' && text[i + 5u] == 'M') *found = 1u;
 }
 
 __device__ __forceinline__ ImpLine imp_line_of(const ImpBatch& B, uint32_t line) {
@@ -284,6 +316,11 @@ struct DeviceImporter::Impl {
   std::vector<Batch> batches;
   uint64_t total_slots = 0, total_cells = 0;
   bool finished = false;
+  // BGZF input
+  int inflate_mode = DeviceImporter::kInflateAuto;
+  BgzfDeviceInflater inflater;
+  DBuf<char> d_win[2];               // the window and the one the carried partial line moves to
+  DBuf<unsigned long long> d_find;
 
   ImpTables tables(int n_samples) const {
     ImpTables T = H.view(opt, n_samples);
@@ -300,16 +337,25 @@ struct DeviceImporter::Impl {
     for (Batch& b : batches) { if (b.key) (void)hipFree(b.key); if (b.src) (void)hipFree(b.src); if (b.size) (void)hipFree(b.size); if (b.tag) (void)hipFree(b.tag); if (b.cells) (void)hipFree(b.cells); }
     batches.clear();
   }
-  uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp);   // -> lines of the batch
+  // text: host text to upload, or null when the batch is already in d_text; -> lines of the batch
+  uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp);
+  int upload_samples(const ImportHeader& hdr);                              // -> imported samples of the file
+  void append_text(const ImportFile& file, const std::string& text);        // inflated text of a whole file, on the host
+  void append_bgzf(const ImportFile& file, const std::string& raw, const std::vector<BgzfMember>& mem);
+  void find_newlines(const char* text, uint64_t lo, uint64_t mid, uint64_t hi, uint64_t* last_below, uint64_t* first_above);
 };
 
-DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes) : m_(new Impl) {
+DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes, int inflate_mode) : m_(new Impl) {
   try {
+    if (inflate_mode < kInflateAuto || inflate_mode > kInflateDevice) throw VCF2BinaryException("inflate mode " + std::to_string(inflate_mode) + ": 0 (auto), 1 (host) or 2 (device)");
+    m_->inflate_mode = inflate_mode;
     m_->device = device;
     m_->opt = opt;
     m_->budget = text_budget_bytes ? text_budget_bytes : kDefaultTextBudget;
     m_->budget = std::min<uint64_t>(m_->budget, (uint64_t)1 << 30);
     if (const char* e = getenv("GDBAMD_IMPORT_STAGE_LDS")) m_->stage_in_lds = atoi(e) != 0;
+    // the A/B of profiles/device_inflate.md: one thread per BGZF member instead of one wavefront (9.6 x slower; kept for that comparison)
+    if (const char* e = getenv("GDBAMD_INFLATE_KERNEL")) m_->inflater.set_kernel(std::string(e) == "thread" ? BgzfDeviceInflater::kThreadPerMember : BgzfDeviceInflater::kWavePerMember);
     m_->H = build_import_tables(vid);                 // the refusals: before the device is touched
     m_->files = import_files(vid, opt);
     Impl& M = *m_;
@@ -338,6 +384,7 @@ DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOpt
     IMP_HIP_CHECK(hipMemset(M.d_counters.p, 0, 4 * sizeof(unsigned long long)));
     M.d_err.ensure(kErrWords);
     M.d_ndef.ensure(1);
+    M.d_find.ensure(2);
   } catch (...) { this->~DeviceImporter(); throw; }
 }
 
@@ -355,6 +402,30 @@ const ImportStats& DeviceImporter::stats() const { return m_->st; }
 
 void DeviceImporter::import_all() { for (const ImportFile& f : m_->files) append_file(f.name); }
 
+namespace {
+uint64_t file_bytes(const std::string& path) { struct stat sb; return stat(path.c_str(), &sb) == 0 ? (uint64_t)sb.st_size : 0u; }
+std::string bad_member(const std::string& path, uint64_t offset, const std::string& why) {
+  return "corrupt BGZF member at byte offset " + std::to_string(offset) + " of " + path + ": " + why;
+}
+// one member by zlib, appended to `out`; the same three checks as on the device
+void inflate_member_host(const std::string& raw, const BgzfMember& m, std::string& out, const std::string& path) {
+  const size_t old = out.size();
+  out.resize(old + (size_t)m.isize + 1u);
+  z_stream zs;
+  memset(&zs, 0, sizeof(zs));
+  if (inflateInit2(&zs, -15) != Z_OK) throw VCF2BinaryException("zlib inflateInit2 failed");
+  zs.next_in = (Bytef*)(raw.data() + m.offset + m.data_off); zs.avail_in = m.data_len;
+  zs.next_out = (Bytef*)(&out[old]); zs.avail_out = m.isize + 1u;
+  const int rc = inflate(&zs, Z_FINISH);
+  const uint64_t got = zs.total_out;
+  inflateEnd(&zs);
+  out.resize(old + (size_t)std::min<uint64_t>(got, m.isize));
+  if (rc != Z_STREAM_END) throw VCF2BinaryException(bad_member(path, m.offset, "invalid DEFLATE stream"));
+  if (got != m.isize) throw VCF2BinaryException(bad_member(path, m.offset, "the data is not ISIZE bytes long"));
+  if ((uint32_t)crc32(0L, (const Bytef*)(out.data() + old), m.isize) != m.crc) throw VCF2BinaryException(bad_member(path, m.offset, "CRC32 mismatch"));
+}
+}  // namespace
+
 void DeviceImporter::append_file(const std::string& filename) {
   Impl& M = *m_;
   IMP_HIP_CHECK(hipSetDevice(M.device));
@@ -362,23 +433,65 @@ void DeviceImporter::append_file(const std::string& filename) {
   for (const ImportFile& f : M.files) if (f.name == filename) file = &f;
   if (!file) throw VCF2BinaryException("file " + filename + " is not in the callset mapping");
   const double t0 = now_s();
+  std::string raw;
+  std::vector<BgzfMember> mem;
+  bool is_bgzf = false;
+  if (M.inflate_mode != kInflateHost) {
+    std::ifstream in(file->path, std::ios::binary);
+    if (!in) throw VCF2BinaryException("cannot open " + file->path);
+    // the first member's header decides: a file that does not begin like BGZF is not read here at all
+    char first[18];
+    in.read(first, sizeof(first));
+    if (in.gcount() == (std::streamsize)sizeof(first) && bgzf_begins((const uint8_t*)first)) {
+      in.clear();
+      in.seekg(0, std::ios::end);
+      const std::streamoff size = in.tellg();
+      in.seekg(0, std::ios::beg);
+      raw.resize(size > 0 ? (size_t)size : 0);
+      if (!raw.empty() && !in.read(&raw[0], (std::streamsize)raw.size())) throw VCF2BinaryException("cannot read " + file->path);
+      is_bgzf = bgzf_walk((const uint8_t*)raw.data(), raw.size(), mem, nullptr);
+    }
+  }
+  if (is_bgzf) {
+    M.st.s_read += now_s() - t0;
+    M.st.compressed_bytes += raw.size();
+    ++M.st.num_files;
+    M.append_bgzf(*file, raw, mem);
+    return;
+  }
+  if (M.inflate_mode == kInflateDevice)
+    throw VCF2BinaryException(file->path + " is not a BGZF file from its first byte to its last, and inflating on the device was required");
+  raw = std::string();
   std::string text;
   try { text = gz_text::read_all(file->path); }
   catch (const std::exception&) { throw VCF2BinaryException("cannot open " + file->path); }
   M.st.s_read += now_s() - t0;
+  M.st.compressed_bytes += file_bytes(file->path);
   ++M.st.num_files;
-  const ImportHeader hdr = parse_import_header(text, *file);
+  ++M.st.num_host_inflated_files;
+  M.append_text(*file, text);
+}
+
+int DeviceImporter::Impl::upload_samples(const ImportHeader& hdr) {
   std::vector<int32_t> samp_idx;
   std::vector<int64_t> samp_row;
   for (int s = 0; s < hdr.n_samples; ++s) if (hdr.sample_row[(size_t)s] >= 0) { samp_idx.push_back(s); samp_row.push_back(hdr.sample_row[(size_t)s]); }
   const int n_imp = (int)samp_idx.size();
-  M.d_samp_idx.ensure(std::max(n_imp, 1));
-  M.d_samp_row.ensure(std::max(n_imp, 1));
+  d_samp_idx.ensure(std::max(n_imp, 1));
+  d_samp_row.ensure(std::max(n_imp, 1));
   if (n_imp) {
-    IMP_HIP_CHECK(hipMemcpyAsync(M.d_samp_idx.p, samp_idx.data(), (size_t)n_imp * sizeof(int32_t), hipMemcpyHostToDevice, M.stream));
-    IMP_HIP_CHECK(hipMemcpyAsync(M.d_samp_row.p, samp_row.data(), (size_t)n_imp * sizeof(int64_t), hipMemcpyHostToDevice, M.stream));
-    IMP_HIP_CHECK(hipStreamSynchronize(M.stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(d_samp_idx.p, samp_idx.data(), (size_t)n_imp * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(d_samp_row.p, samp_row.data(), (size_t)n_imp * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
   }
+  return n_imp;
+}
+
+void DeviceImporter::Impl::append_text(const ImportFile& file_, const std::string& text) {
+  const ImportFile* file = &file_;
+  Impl& M = *this;
+  const ImportHeader hdr = parse_import_header(text, *file);
+  const int n_imp = upload_samples(hdr);
   // batches of at most the budget, cut behind a newline; a line longer than the budget grows its batch
   size_t pos = hdr.record_begin;
   int64_t lines_before = hdr.lines_before;
@@ -397,17 +510,147 @@ void DeviceImporter::append_file(const std::string& filename) {
   }
 }
 
+void DeviceImporter::Impl::find_newlines(const char* text, uint64_t lo, uint64_t mid, uint64_t hi, uint64_t* last_below, uint64_t* first_above) {
+  unsigned long long r[2] = {0ull, ~0ull};
+  if (hi > lo) {
+    IMP_HIP_CHECK(hipMemcpyAsync(d_find.p, r, sizeof(r), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_imp_find_newlines, dim3(grid_for(hi - lo)), dim3(kBlock), 0, stream, text, lo, mid, hi, d_find.p);
+    IMP_HIP_CHECK(hipMemcpyAsync(r, d_find.p, sizeof(r), hipMemcpyDeviceToHost, stream));
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  *last_below = r[0];
+  *first_above = r[1];
+}
+
+void DeviceImporter::Impl::append_bgzf(const ImportFile& file, const std::string& raw, const std::vector<BgzfMember>& mem) {
+  // ---- the '#' lines: leading members on the host, until a record line has begun
+  double t0 = now_s();
+  std::string head;
+  size_t k = 0, line_start = 0;
+  bool complete = false;
+  while (!complete && k < mem.size()) {
+    inflate_member_host(raw, mem[k], head, file.path);
+    ++k;
+    for (;;) {
+      const size_t nl = head.find('\n', line_start);
+      const size_t e = nl == std::string::npos ? head.size() : nl;
+      size_t ln = e - line_start;
+      if (ln && head[e - 1] == '\r') --ln;
+      if (ln && head[line_start] != '#') { complete = true; break; }
+      if (nl == std::string::npos) break;      // a '#' line (or nothing yet) that the next member continues
+      line_start = nl + 1;
+    }
+  }
+  st.s_read += now_s() - t0;
+  const ImportHeader hdr = parse_import_header(head, file);
+  const int n_imp = upload_samples(hdr);
+  const std::string chrom_error = "a #CHROM line after the first record in " + file.path + " is not imported by the device importer of this build";
+
+  // ---- windows: [carried partial line | members k .. k2)
+  int cur = 0;
+  uint64_t carry = head.size() - hdr.record_begin;
+  if (carry >= ((uint64_t)1 << 31)) throw VCF2BinaryException("a record line of 2 GiB or more in " + file.path);
+  d_win[cur].ensure((size_t)carry + 16);
+  if (carry) {
+    t0 = now_s();
+    IMP_HIP_CHECK(hipMemcpyAsync(d_win[cur].p, head.data() + hdr.record_begin, (size_t)carry, hipMemcpyHostToDevice, stream));
+    st.bytes_h2d += carry;
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
+    st.s_h2d += now_s() - t0;
+  }
+  int64_t lines_before = hdr.lines_before;
+  for (;;) {
+    size_t k2 = k;
+    uint64_t w_bytes = 0;
+    const uint64_t room = budget > carry ? budget - carry : 0;
+    while (k2 < mem.size() && (k2 == k || w_bytes + mem[k2].isize <= room)) w_bytes += mem[k2++].isize;
+    const bool last = k2 == mem.size();
+    const uint64_t wend = carry + w_bytes;
+    if (d_win[cur].cap < wend + 16) {          // grows, and keeps the carried bytes
+      d_win[1 - cur].ensure((size_t)wend + 16);
+      if (carry) IMP_HIP_CHECK(hipMemcpyAsync(d_win[1 - cur].p, d_win[cur].p, (size_t)carry, hipMemcpyDeviceToDevice, stream));
+      cur = 1 - cur;
+    }
+    char* win = d_win[cur].p;
+    if (k2 > k) {
+      const float ms_before = inflater.ms_kernel, up_before = inflater.ms_upload;
+      const uint64_t h2d_before = inflater.bytes_h2d;
+      uint32_t err = 0;
+      const int64_t bad = inflater.inflate((const uint8_t*)raw.data(), mem.data(), k, k2, (uint8_t*)win + carry, (void*)stream, &err);
+      st.ms_inflate += inflater.ms_kernel - ms_before;
+      st.bytes_h2d += inflater.bytes_h2d - h2d_before;
+      st.s_h2d += (double)(inflater.ms_upload - up_before) * 1e-3;
+      if (bad >= 0) throw VCF2BinaryException(bad_member(file.path, mem[(size_t)bad].offset, bgzf_inflate_error_text(err)));
+      st.num_device_members += (int64_t)(k2 - k);
+    }
+    char last_byte = '\n';
+    if (wend) {
+      uint32_t found = 0;
+      IMP_HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(uint32_t), stream));
+      hipLaunchKernelGGL(k_imp_find_chrom, dim3(grid_for(wend)), dim3(kBlock), 0, stream, (const char*)win, wend, d_err.p);
+      IMP_HIP_CHECK(hipMemcpyAsync(&found, d_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      if (last) IMP_HIP_CHECK(hipMemcpyAsync(&last_byte, win + wend - 1, 1, hipMemcpyDeviceToHost, stream));
+      IMP_HIP_CHECK(hipStreamSynchronize(stream));
+      if (found) throw VCF2BinaryException(chrom_error);
+    }
+    // batches of at most the budget, cut behind a newline; a line longer than the budget grows its batch
+    uint64_t pos = 0;
+    while (pos < wend) {
+      uint64_t stop = wend, below = 0, above = 0;
+      if (wend - pos > budget) {
+        find_newlines(win, pos, pos + budget, wend, &below, &above);
+        if (below) stop = below;
+        else if (above != ~(uint64_t)0) stop = above + 1;
+        else if (!last) break;                 // the line goes on in the next window
+      } else if (!last) {
+        find_newlines(win, pos, wend, wend, &below, &above);
+        if (!below) break;
+        stop = below;
+      }
+      const uint64_t n = stop - pos;
+      if (n >= ((uint64_t)1 << 31)) throw VCF2BinaryException("a record line of 2 GiB or more in " + file.path);
+      const bool add_newline = stop == wend && last && last_byte != '\n';
+      d_text.ensure((size_t)n + 1 + kTextPad);
+      IMP_HIP_CHECK(hipMemcpyAsync(d_text.p, win + pos, (size_t)n, hipMemcpyDeviceToDevice, stream));
+      lines_before += batch(file, hdr, nullptr, (size_t)n, add_newline, lines_before, n_imp);
+      pos = stop;
+    }
+    carry = wend - pos;
+    if (last) break;
+    if (carry >= ((uint64_t)1 << 31)) throw VCF2BinaryException("a record line of 2 GiB or more in " + file.path);
+    if (pos) {                                 // the partial line moves to the front of the next window
+      d_win[1 - cur].ensure(std::max((size_t)carry + 16, d_win[cur].cap));      // (as large as this one: the next window fits without a second move)
+      if (carry) IMP_HIP_CHECK(hipMemcpyAsync(d_win[1 - cur].p, win + pos, (size_t)carry, hipMemcpyDeviceToDevice, stream));
+      cur = 1 - cur;
+    }
+    k = k2;
+  }
+}
+
 uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n_text, bool add_newline, int64_t lines_before, int n_imp) {
   const uint32_t n = (uint32_t)(n_text + (add_newline ? 1 : 0));
   ++st.num_batches;
   st.text_bytes += n_text;
   double t0 = now_s();
-  d_text.ensure((size_t)n + kTextPad);
-  IMP_HIP_CHECK(hipMemcpyAsync(d_text.p, text, n_text, hipMemcpyHostToDevice, stream));
+  if (text) {
+    d_text.ensure((size_t)n + kTextPad);
+    IMP_HIP_CHECK(hipMemcpyAsync(d_text.p, text, n_text, hipMemcpyHostToDevice, stream));
+    st.bytes_h2d += n_text;
+  } else if (d_text.cap < (size_t)n + kTextPad) throw GenomicsDBDeviceException("batch text is not in d_text");
   if (add_newline) IMP_HIP_CHECK(hipMemsetAsync(d_text.p + n_text, '\n', 1, stream));
   IMP_HIP_CHECK(hipMemsetAsync(d_text.p + n, 0, kTextPad, stream));
   IMP_HIP_CHECK(hipStreamSynchronize(stream));
-  st.s_h2d += now_s() - t0;
+  if (text) st.s_h2d += now_s() - t0;
+  // text that was inflated on the device comes to the host only when a deferred token or an error message needs it
+  std::string text_copy;
+  auto host_text = [&]() -> const char* {
+    if (text) return text;
+    if (text_copy.empty() && n_text) {
+      text_copy.resize(n_text);
+      IMP_HIP_CHECK(hipMemcpy(&text_copy[0], d_text.p, n_text, hipMemcpyDeviceToHost));
+    }
+    return text_copy.data();
+  };
 
   // ---- index
   const uint32_t n_tiles = (n + kTile - 1u) / kTile;
@@ -499,7 +742,7 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
     const ImpDeferred& d = def[i];
     if ((uint64_t)d.tok_off + d.tok_len > n_text) throw GenomicsDBDeviceException("deferred token outside the batch");
     patch_at[i] = d.out_off;
-    try { patch_val[i] = resolve_deferred(d, text, H); }
+    try { patch_val[i] = resolve_deferred(d, host_text(), H); }
     catch (const VCF2BinaryException& e) {
       if (d.line < bad_line) { bad_line = d.line; bad_text = e.what(); bad_text = bad_text.substr(strlen("VCF2BinaryException : ")); }
     }
@@ -515,7 +758,7 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
       if (line) { IMP_HIP_CHECK(hipMemcpy(&lb, d_nl.p + (line - 1), sizeof(uint32_t), hipMemcpyDeviceToHost)); ++lb; }
       IMP_HIP_CHECK(hipMemcpy(&le, d_nl.p + line, sizeof(uint32_t), hipMemcpyDeviceToHost));
       le = std::min<uint32_t>(le, (uint32_t)n_text);
-      throw VCF2BinaryException(describe_line_error(err_bit, H, opt, hdr, text, lb, le, where));
+      throw VCF2BinaryException(describe_line_error(err_bit, H, opt, hdr, host_text(), lb, le, where));
     }
     throw VCF2BinaryException(bad_text + " (" + where + ")");
   }
@@ -599,9 +842,10 @@ void DeviceImporter::finish(std::vector<uint8_t>& cells) {
   M.free_batches();
 }
 
-std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes, ImportStats* stats) {
+std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes, ImportStats* stats,
+                                                     int inflate_mode) {
   const double t0 = now_s();
-  DeviceImporter imp(device, vid, opt, text_budget_bytes);
+  DeviceImporter imp(device, vid, opt, text_budget_bytes, inflate_mode);
   imp.import_all();
   std::vector<uint8_t> out;
   imp.finish(out);

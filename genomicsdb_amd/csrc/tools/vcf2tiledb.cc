@@ -1,12 +1,13 @@
 // vcf2tiledb - command line of the reference's import tool for what this build implements:
-//   vcf2tiledb [-r <rank>] [--import-on-device] <loader.json>
+//   vcf2tiledb [-r <rank>] [--import-on-device [--inflate-on-host]] <loader.json>
 // (reference: tools/src/vcf2tiledb.cc:54-140; VCF2TileDBLoader::read_all, src/main/cpp/src/loader/tiledb_loader.cc:845-965).
 // The (g)VCFs of the callset mapping are converted to begin-cells of column partition `rank` (host, vcf_importer.cc) and
 //   "produce_tiledb_array": true  -> written to <workspace>/<array>/cells.bin, the array file gt_mpi_gather and the JNI stream open
 //   "produce_combined_vcf": true  -> combined in-line on the GPU (same path as gt_mpi_gather --produce-Broad-GVCF) and written
 //                                    to stdout, like the reference loader's in-line BroadCombinedGVCFOperator
 // --import-on-device: the conversion runs on the rank's GPU (LOCAL_RANK / GDBAMD_DEVICE, as the other tools choose it) and gives the
-// same cells; the default is the host importer.
+// same cells; the default is the host importer.  On the device, bgzip'ed input (BGZF) is inflated there too and crosses the link
+// compressed; --inflate-on-host keeps zlib on the host for every file.
 // The --split-files modes of the reference tool are not implemented (exit with an error).
 #include <getopt.h>
 #include <sys/stat.h>
@@ -35,13 +36,14 @@ static void mkdir_p(const std::string& path) {
 }
 
 int main(int argc, char** argv) {
-  enum { ARG_VERSION = 1000, ARG_UNSUPPORTED, ARG_IMPORT_ON_DEVICE };
+  enum { ARG_VERSION = 1000, ARG_UNSUPPORTED, ARG_IMPORT_ON_DEVICE, ARG_INFLATE_ON_HOST };
   static struct option long_options[] = {{"tmp-directory", 1, 0, 'T'}, {"rank", 1, 0, 'r'}, {"version", 0, 0, ARG_VERSION}, {"import-on-device", 0, 0, ARG_IMPORT_ON_DEVICE},
+                                         {"inflate-on-host", 0, 0, ARG_INFLATE_ON_HOST},
                                          {"split-files", 0, 0, ARG_UNSUPPORTED}, {"split-all-partitions", 0, 0, ARG_UNSUPPORTED},
                                          {"split-files-results-directory", 1, 0, ARG_UNSUPPORTED}, {"split-output-filename", 1, 0, ARG_UNSUPPORTED},
                                          {"split-callset-mapping-file", 0, 0, ARG_UNSUPPORTED}, {0, 0, 0, 0}};
   int rank = launcher_rank();
-  bool import_on_device = false;
+  bool import_on_device = false, inflate_on_host = false;
   int c;
   while ((c = getopt_long(argc, argv, "T:r:", long_options, NULL)) >= 0) {
     switch (c) {
@@ -49,6 +51,7 @@ int main(int argc, char** argv) {
       case 'r': rank = atoi(optarg); break;
       case ARG_VERSION: std::cout << "genomicsdb_amd (MI355X variant-combine path) for GenomicsDB 0.10.2 loader JSON\n"; return 0;
       case ARG_IMPORT_ON_DEVICE: import_on_device = true; break;
+      case ARG_INFLATE_ON_HOST: inflate_on_host = true; break;
       case ARG_UNSUPPORTED: std::cerr << "vcf2tiledb: the --split-files modes are not implemented by this build\n"; return -1;
       default: std::cerr << "Unknown command line argument\n"; return -1;
     }
@@ -73,10 +76,13 @@ int main(int argc, char** argv) {
     ImportStats st;
     int device = 0;
     if (const char* e = getenv("GDBAMD_DEVICE")) device = atoi(e); else if (const char* e2 = getenv("LOCAL_RANK")) device = atoi(e2);
-    const std::vector<uint8_t> cells = import_on_device ? import_callsets_to_cells_device(vid, opt, device, 0, &st) : import_callsets_to_cells(vid, opt, &st);
+    const std::vector<uint8_t> cells = import_on_device ? import_callsets_to_cells_device(vid, opt, device, 0, &st, inflate_on_host ? 1 : 0) : import_callsets_to_cells(vid, opt, &st);
     const double t_import = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",vcf2binary,Wall-clock time(s)," << t_import << ",files," << st.num_files << ",records," << st.num_records
               << ",cells," << st.num_cells << ",bytes," << st.num_bytes << ",device," << (import_on_device ? 1 : 0) << ",deferred," << st.num_deferred_values << "\n";
+    if (import_on_device)
+      std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",vcf2binary_inflate,compressed_bytes," << st.compressed_bytes << ",device_members," << st.num_device_members
+                << ",host_inflated_files," << st.num_host_inflated_files << ",inflate_kernel_ms," << st.ms_inflate << "\n";
     const bool produce_array = doc.HasMember("produce_tiledb_array") && doc["produce_tiledb_array"].GetBool();
     if (produce_array) {
       const std::string dir = loader.get_workspace(rank) + "/" + loader.get_array_name(rank);

@@ -125,6 +125,10 @@ int gdbamd_bgzf_compress(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t 
  * newlines; any bytes give a valid stream), 0 = the byte-level kernel ("b", and what gdbamd_bgzf_compress runs) */
 int gdbamd_bgzf_compress_mode(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* dst_len, float* ms_kernels, int vcf_text);
 uint64_t gdbamd_bgzf_bound(uint64_t n);
+/* the counterpart: a whole BGZF buffer (a chain of members from its first byte to its last, the EOF member included or not) inflated on GPU
+ * `device` by the kernel the device importer uses, one wavefront per member; stream, ISIZE and CRC32 of every member are verified there.
+ * *dst_len = the inflated size; dst NULL: only that (no device needed).  0 on success; a bad member is an error that names its byte offset. */
+int gdbamd_bgzf_decompress(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* dst_len, float* ms_kernels, int device);
 void gdbamd_engine_destroy(void* engine);
 int gdbamd_engine_num_fields(void* engine);                                     /* plan fields = staged attribute columns */
 const char* gdbamd_engine_field_name(void* engine, int f);                      /* array attribute name of plan field f */
@@ -249,7 +253,7 @@ int gdbamd_column_partition(const char* loader_json_text, int rank, int64_t* beg
 int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                         int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells);
 /* The same import with the conversion on GPU `device` (kernels/gdb_import.hip): byte for byte the cells of gdbamd_import_cells.
- * The host reads and inflates the files; the device indexes, measures, writes, sorts and gathers.  text_budget_bytes: record text
+ * The host reads the files; the device inflates BGZF input (see below), indexes, measures, writes, sorts and gathers.  text_budget_bytes: record text
  * per batch (0: default).  Numeric tokens outside the device's exact fast path are parsed by the host importer's functions
  * (stats slot 5 counts them).  Refused with an error that names the field: 2-dimensional (allele-specific) fields and flattened
  * tuple elements - gdbamd_import_cells serves those vids.  stats: NULL or GDBAMD_IMPORT_NUM_STATS doubles:
@@ -259,6 +263,18 @@ int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mappin
 int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                                int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
                                double* stats);
+/* The same with the inflate mode chosen and more statistics.  A BGZF file - gzip members with the "BC" subfield from the first byte to the last,
+ * what bgzip and htslib write - crosses the link compressed: the host inflates only the members that hold the '#' lines, the device the rest
+ * (kernels/gdb_inflate.hip), in windows of about text_budget_bytes, and verifies stream, ISIZE and CRC32 of every member; a member that fails
+ * refuses the file with an error that names the file and the member's byte offset.  inflate_mode: 0 auto (BGZF on the device, every other file
+ * through zlib on the host), 1 always on the host, 2 a file that is not BGZF is an error.  gdbamd_import_cells_device is this call with mode 0.
+ * stats: NULL or nstats doubles; slots 0..16 as above, then 17 bytes of the input files as stored, 18 BGZF members inflated on the device,
+ * 19 files inflated whole on the host, 20 HIP-event ms of the inflate kernel, 21 input bytes uploaded (text, or compressed members).
+ * Batches never cross a window, so slot 6 (batches) can be larger than with inflate on the host for the same budget; the cells are the same. */
+#define GDBAMD_IMPORT_NUM_STATS_EX 22
+int gdbamd_import_cells_device_ex(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                                  int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
+                                  int inflate_mode, double* stats, int nstats);
 void gdbamd_free(void* p);
 
 #ifdef __cplusplus
