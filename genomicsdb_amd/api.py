@@ -361,16 +361,22 @@ INFLATE_MODES = {"auto": 0, "host": 1, "device": 2}
 
 
 def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_deletions_as_intervals=True, column_begin=0, column_end=2**63 - 2,
-                 device=None, text_budget_bytes=0, stats=None, inflate="auto"):
+                 device=None, text_budget_bytes=0, stats=None, inflate="auto", streams=None):
     """(g)VCFs of a callset mapping -> begin-cells (bytes, reference binary cell layout, column-major) of one column partition:
     the conversion step of the reference's vcf2tiledb (vcf2binary.cc:991-1196).
     device=None: host code, no device needed.  device=<int>: the conversion runs on that GPU (kernels/gdb_import.hip) and gives
     the same bytes; text_budget_bytes is the record text per batch (0: default) and `stats`, a dict, receives IMPORT_STAT_NAMES.
     inflate (device path only): "auto" - bgzip'ed (BGZF) files cross the link compressed and are inflated on the device
     (kernels/gdb_inflate.hip), every other file goes through zlib on the host; "host" - zlib for every file; "device" - a file that
-    is not BGZF is an error.  A BGZF member with a bad stream, ISIZE or CRC32 refuses the import."""
+    is not BGZF is an error.  A BGZF member with a bad stream, ISIZE or CRC32 refuses the import.
+    BCF2 (device path only): a file whose content - plain, BGZF or gzip - begins with 'BCF\\2\\1' or 'BCF\\2\\2' is imported as BCF2 and
+    gives the cells of the same records as VCF text; compressed BCF2 is inflated on the host (inflate="device" refuses it), and the
+    host importer refuses a BCF2 file by name.  streams (device path only): {name: bytes} - a callset whose "filename" equals a name is
+    read from those bytes (VCF text or BCF2, plain or gzip) instead of a file; a name that no callset uses is an error."""
     if inflate not in INFLATE_MODES:
         raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
+    if streams is not None and device is None:
+        raise ValueError("streams= needs device=: the host importer reads files only")
     L = _lib.lib()
     p = ctypes.c_void_p()
     n = ctypes.c_uint64()
@@ -380,9 +386,14 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
                                    column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc))
     else:
         st = (ctypes.c_double * len(IMPORT_STAT_NAMES))()
-        rc = L.gdbamd_import_cells_device_ex(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
-                                             1 if treat_deletions_as_intervals else 0, column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc),
-                                             int(device), int(text_budget_bytes), INFLATE_MODES[inflate], st, len(IMPORT_STAT_NAMES))
+        items = [(os.fsencode(k), bytes(v)) for k, v in (streams or {}).items()]
+        ns = len(items)
+        names = (ctypes.c_char_p * max(ns, 1))(*[k for k, _ in items])
+        data = (ctypes.c_void_p * max(ns, 1))(*[ctypes.cast(ctypes.c_char_p(v), ctypes.c_void_p) for _, v in items])      # (items keeps the bytes alive)
+        sizes = (ctypes.c_uint64 * max(ns, 1))(*[len(v) for _, v in items])
+        rc = L.gdbamd_import_cells_device_streams(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
+                                                  1 if treat_deletions_as_intervals else 0, column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc),
+                                                  int(device), int(text_budget_bytes), INFLATE_MODES[inflate], st, len(IMPORT_STAT_NAMES), ns, names, data, sizes)
         if rc == 0 and stats is not None:
             stats.update({k: (float(v) if k[:2] in ("ms", "s_") else int(v)) for k, v in zip(IMPORT_STAT_NAMES, st)})
     _check(rc == 0, "import_cells")

@@ -123,6 +123,14 @@ def build_hostsim_import():
     return os.path.join(ROOT, "tests", "hostsim_import", "libhostsim_import.so")
 
 
+def build_hostsim_import_bcf():
+    """CPU harness around the bodies of the device importer's BCF2 path (core/gdb_import_bcf.hpp) and the stand-alone
+    malformed-input program built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_import_bcf")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_import_bcf.so"), os.path.join(d, "malformed_bcf")
+
+
 def build_hostsim_inflate():
     """CPU harness around the bodies of the BGZF inflater (core/gdb_inflate.hpp; tests only)"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_inflate")])

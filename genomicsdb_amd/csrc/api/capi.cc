@@ -459,8 +459,23 @@ int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset
 int gdbamd_import_cells_device_ex(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                                   int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
                                   int inflate_mode, double* stats, int nstats) {
+  return gdbamd_import_cells_device_streams(vid_mapping_file, callset_mapping_file, file_root, treat_deletions_as_intervals, column_begin, column_end, cells, nbytes, ncells,
+                                            device, text_budget_bytes, inflate_mode, stats, nstats, 0, nullptr, nullptr, nullptr);
+}
+int gdbamd_import_cells_device_streams(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                                       int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device,
+                                       uint64_t text_budget_bytes, int inflate_mode, double* stats, int nstats, int nstreams, const char* const* names,
+                                       const void* const* data, const uint64_t* stream_nbytes) {
   try {
     if (!vid_mapping_file || !callset_mapping_file || !cells || !nbytes) throw GenomicsDBConfigException("gdbamd_import_cells_device: null argument");
+    if (nstreams < 0 || (nstreams > 0 && (!names || !data || !stream_nbytes))) throw GenomicsDBConfigException("gdbamd_import_cells_device_streams: null stream arrays");
+    std::vector<ImportStream> streams;
+    for (int i = 0; i < nstreams; ++i) {
+      if (!names[i]) throw GenomicsDBConfigException("gdbamd_import_cells_device_streams: null stream name");
+      ImportStream s;
+      s.name = names[i]; s.data = data[i]; s.nbytes = stream_nbytes[i];
+      streams.push_back(s);
+    }
     VidMapper vid;
     vid.parse_vid_json(mini_json::parse_file(vid_mapping_file));
     vid.parse_callsets_json(mini_json::parse_file(callset_mapping_file));
@@ -470,7 +485,7 @@ int gdbamd_import_cells_device_ex(const char* vid_mapping_file, const char* call
     opt.column_end = column_end;
     if (file_root) opt.file_root = file_root;
     ImportStats st;
-    const std::vector<uint8_t> out = import_callsets_to_cells_device(vid, opt, device, text_budget_bytes, &st, inflate_mode);
+    const std::vector<uint8_t> out = import_callsets_to_cells_device(vid, opt, device, text_budget_bytes, &st, inflate_mode, streams);
     *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
     if (!*cells) throw GenomicsDBConfigException("out of memory");
     if (!out.empty()) memcpy(*cells, out.data(), out.size());

@@ -255,6 +255,8 @@ std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const Import
   for (const std::string& fn : files) {
     const std::string path = (!fn.empty() && fn[0] != '/' && !opt.file_root.empty()) ? opt.file_root + "/" + fn : fn;
     const std::string text = read_text_maybe_gz(path);
+    if (text.size() >= 5 && memcmp(text.data(), "BCF\2", 4) == 0 && (text[4] == 1 || text[4] == 2))      // the content decides, plain or compressed
+      throw VCF2BinaryException(path + " is BCF2: BCF2 input needs the device importer (import_callsets_to_cells_device, vcf2tiledb --import-on-device); the host importer reads VCF text");
     ++st.num_files;
     std::vector<int64_t> sample_row;   // file sample idx -> array row (-1: not imported)
     int n_samples = 0;

@@ -11,8 +11,8 @@
 //          [INFO attributes in vid order][FORMAT attributes in vid order]
 //          fixed-length attribute = num x element (missing: TileDB null), var-length = i32 num + num x element (missing: num 0)
 //
-// Not done (documented in DESIGN.md): htslib's record-level checks, CSV / buffer-stream inputs, fields of more than 2
-// dimensions.  2-dimensional (allele-specific) fields and intervals that reach across a partition begin ARE imported by
+// Not done (documented in DESIGN.md): htslib's record-level checks, CSV input, fields of more than 2 dimensions.  BCF2 files
+// and buffer streams are read by the device path only (host/import_bcf.hpp); import_callsets_to_cells refuses a BCF2 file by name.  2-dimensional (allele-specific) fields and intervals that reach across a partition begin ARE imported by
 // import_callsets_to_cells; the device path (import_callsets_to_cells_device, kernels/gdb_import.hip) refuses 2-dimensional
 // fields and flattened tuple elements by name and leaves those vids to the host importer.
 #pragma once
@@ -58,8 +58,13 @@ std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const Import
 // inflate_mode: 0 BGZF files are inflated on the device and every other file on the host, 1 always on the host, 2 a file that is
 // not BGZF is an error.  Refuses, before any launch, 2-dimensional fields, flattened tuple elements and what
 // import_callsets_to_cells refuses; a BGZF member whose stream, ISIZE or CRC32 is wrong refuses the file.
+// BCF2 files (sniffed by content, plain or compressed) are imported too; compressed BCF2 is inflated on the host and is an error in
+// inflate_mode 2.  streams: a callset file whose "filename" equals a stream's name is read from that memory instead (VCF text or
+// BCF2, plain or gzip); a stream that no callset names is an error.
+struct ImportStream { std::string name; const void* data = nullptr; uint64_t nbytes = 0; };
 std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes,
-                                                     ImportStats* stats = nullptr, int inflate_mode = 0);
+                                                     ImportStats* stats = nullptr, int inflate_mode = 0,
+                                                     const std::vector<ImportStream>& streams = std::vector<ImportStream>());
 
 // the importer's number parsers (strtoll / strtod over the whole token, VCF2BinaryException otherwise): the device path runs
 // them on the tokens it deferred

@@ -5,7 +5,10 @@
 // inflated on the host, the rest on the device (kernels/gdb_inflate.hip), in windows of about one text budget; every other file is
 // inflated on the host and its text uploaded.  Per batch the device indexes newlines and tabs, measures one cell per
 // (record line, imported sample), lays the cells out by a scan and writes them - the bodies of core/gdb_import.hpp, the same
-// bytes as host/vcf_importer.cc.  finish() resolves the intervals that span the partition begin, sorts all cells by
+// bytes as host/vcf_importer.cc.  BCF2 input (a file or a stream in memory, sniffed by content; compressed BCF2 is inflated on the
+// host) takes the same path with another index pass: the host walks the l_shared / l_indiv chain and cuts batches at record
+// boundaries, the device indexes each record once (core/gdb_import_bcf.hpp) and measures and writes per (record, sample).
+// finish() resolves the intervals that span the partition begin, sorts all cells by
 // (column, row) with ties in append order, gathers them into column-major order and copies the result out once.
 #pragma once
 #include <cstdint>
@@ -26,8 +29,13 @@ class DeviceImporter {
   ~DeviceImporter();
   DeviceImporter(const DeviceImporter&) = delete;
   DeviceImporter& operator=(const DeviceImporter&) = delete;
-  void import_all();                                  // append_file for every file of the callset mapping, in mapping order
-  void append_file(const std::string& filename);      // a "filename" of the callset mapping
+  // every file of the callset mapping, in mapping order: append_buffer where a stream has the file's name, else append_file
+  void import_all(const std::vector<ImportStream>& streams = std::vector<ImportStream>());
+  // a "filename" of the callset mapping.  The content decides: VCF text or BCF2 ('BCF\2\1' / 'BCF\2\2'), plain, gzip or BGZF
+  void append_file(const std::string& filename);
+  // the same from memory (the buffer-stream input of the reference's importer): `name` is a "filename" of the callset mapping whose
+  // content is the nbytes at ptr, sniffed like a file's
+  void append_buffer(const std::string& name, const void* ptr, uint64_t nbytes);
   void finish(std::vector<uint8_t>& cells);
   const ImportStats& stats() const;
  private:

@@ -20,6 +20,12 @@
 // front of the next one, so a batch never crosses a window: with the same budget, num_batches can be larger than for the same text
 // inflated on the host (the cells do not depend on where batches are cut), and each cut costs one small launch and round trip.  Every other file (plain text, plain gzip, a chain that breaks) is inflated by gz_text::read_all and
 // its text uploaded, as before.
+//
+// BCF2 input (a file or a buffer whose inflated bytes begin with 'BCF\2\1' / 'BCF\2\2'; compressed BCF2 is inflated on the host, because
+// records cross BGZF members): the host parses the header and walks the l_shared / l_indiv chain (host/import_bcf.hpp), cuts batches at
+// record boundaries and uploads the bytes and the record offsets; k_imp_bcf_index - one thread per record - takes the place of the
+// newline / tab index and leaves a table per record (core/gdb_import_bcf.hpp); measure, write and finish() are the kernels above,
+// instantiated over ImpBcfSrc instead of ImpTextSrc, one thread per (record, imported sample).
 #include "gdb_import.h"
 
 #include <hip/hip_runtime.h>
@@ -33,8 +39,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 
 #include "../common/gz_text.hpp"
+#include "../host/import_bcf.hpp"
 #include "../host/import_common.hpp"
 #include "gdb_inflate.h"
 #include "gdb_pipeline.h"
@@ -150,20 +158,56 @@ __device__ __forceinline__ void imp_raise(uint32_t* err, uint32_t bits, uint32_t
 struct ImpSamples { const int32_t* file_idx; const int64_t* row; int32_t n; };    // imported samples of the file
 struct ImpSpan { unsigned long long* row_best; int32_t seq_bits; uint64_t line_seq_base; int64_t max_row; };   // row_best null: no partition begin
 
+// Where the slots of a batch come from: record lines of text (index: newlines and tabs) or BCF2 records (index: k_imp_bcf_index).
+// measure / write are the two passes of one (line or record, sample of the file); is_record: the line counts as a record.
+struct ImpTextSrc {
+  ImpBatch B;
+  __device__ __forceinline__ ImpSlot measure(const ImpTables& T, uint32_t line, int sample, bool* is_record) const {
+    const ImpLine L = imp_line_of(B, line);
+    *is_record = L.end > L.begin && B.text[L.begin] != '#';
+    return imp_measure(T, L, sample);
+  }
+  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t line, int sample, int64_t row, const ImpSlot& s, ImpSink<true>& o) const {
+    return imp_write(T, imp_line_of(B, line), sample, row, s, o);
+  }
+};
+struct ImpBcfSrc {
+  ImpBcfTables BT; const uint8_t* bytes; const ImpBcfRec* rec; const ImpBcfField* fld; uint32_t n_attr;
+  __device__ __forceinline__ ImpSlot measure(const ImpTables& T, uint32_t r, int sample, bool* is_record) const {
+    *is_record = true;
+    return imp_bcf_measure(T, BT, bytes, rec[r], fld + (uint64_t)r * n_attr, sample);
+  }
+  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t r, int sample, int64_t row, const ImpSlot& s, ImpSink<true>& o) const {
+    return imp_bcf_write(T, BT, bytes, rec[r], fld + (uint64_t)r * n_attr, sample, row, s, o);
+  }
+};
+
+// the index pass of a BCF2 batch: one thread per record walks the shared block and the FORMAT blocks once (core/gdb_import_bcf.hpp)
+__global__ void __launch_bounds__(kBlock) k_imp_bcf_index(ImpTables T, ImpBcfTables BT, const uint8_t* bytes, uint32_t n_bytes, const uint32_t* rec_off, uint32_t n_rec,
+                                                         ImpBcfRec* rec, ImpBcfField* fld, uint32_t n_attr) {
+  const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+  if (r >= n_rec) return;
+  uint32_t b = rec_off[r], e = rec_off[r + 1u];
+  if (e > n_bytes) e = n_bytes;       // (never, by the host's walk: no read leaves the batch)
+  if (b > e) b = e;
+  imp_bcf_index(T, BT, bytes, b, e, &rec[r], fld + (uint64_t)r * n_attr);
+}
+
 // one thread per (record line, imported sample); with no imported sample one thread per line, for the checks and the count
-__global__ void __launch_bounds__(kBlock) k_imp_measure(ImpTables T, ImpBatch B, ImpSamples S, ImpSpan P, uint64_t n_slots, int64_t* col, int64_t* end,
+template <class Src>
+__global__ void __launch_bounds__(kBlock) k_imp_measure(ImpTables T, Src src, ImpSamples S, ImpSpan P, uint64_t n_slots, int64_t* col, int64_t* end,
                                                        uint64_t* size, uint8_t* kind, uint32_t* err, unsigned long long* counters) {
   const uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t per_line = S.n > 0 ? (uint32_t)S.n : 1u;
   bool is_record = false, is_cell = false;
   if (slot < n_slots) {
     const uint32_t line = (uint32_t)(slot / per_line), j = (uint32_t)(slot % per_line);
-    const ImpLine L = imp_line_of(B, line);
     const int sample = S.n > 0 ? S.file_idx[j] : -1;
-    const ImpSlot s = imp_measure(T, L, sample);
-    is_record = j == 0u && L.end > L.begin && B.text[L.begin] != '#';
+    bool record_line = false;
+    const ImpSlot s = src.measure(T, line, sample, &record_line);
+    is_record = j == 0u && record_line;
     if (s.err) imp_raise(err, s.err, line);
-    else if (P.row_best && sample >= 0 && L.end > L.begin && B.text[L.begin] != '#' && s.col <= T.column_end && s.col <= T.column_begin) {
+    else if (P.row_best && sample >= 0 && record_line && s.col <= T.column_end && s.col <= T.column_begin) {
       const int64_t row = S.row[j];
       if (row >= 0 && row <= P.max_row)
         atomicMax(&P.row_best[row], ((unsigned long long)s.col << P.seq_bits) | (unsigned long long)(P.line_seq_base + line + 1u));
@@ -184,8 +228,8 @@ constexpr uint32_t kStageBytes = 64u << 10;   // LDS a block may stage its cells
 // write their cells - byte by byte, as the bodies do - into LDS at the range's own alignment, and the block then stores the range
 // with aligned dwords, consecutive lanes on consecutive words; a block whose cells do not fit writes them directly like STAGE = false
 // (profiles/device_import.md has the A/B).
-template <bool STAGE>
-__global__ void __launch_bounds__(kBlock) k_imp_write(ImpTables T, ImpBatch B, ImpSamples S, ImpSpan P, uint64_t n_slots, const int64_t* col, const int64_t* end,
+template <bool STAGE, class Src>
+__global__ void __launch_bounds__(kBlock) k_imp_write(ImpTables T, Src from, ImpSamples S, ImpSpan P, uint64_t n_slots, const int64_t* col, const int64_t* end,
                                                      const uint64_t* size, const uint8_t* kind, const uint64_t* off, uint8_t* cells, uint64_t cells_bytes,
                                                      ImpDeferred* def, uint32_t* ndef, uint32_t def_cap, uint64_t* key_out, uint64_t* src_out, uint32_t* size_out,
                                                      uint64_t* tag_out, uint32_t* err) {
@@ -207,12 +251,11 @@ __global__ void __launch_bounds__(kBlock) k_imp_write(ImpTables T, ImpBatch B, I
       const uint64_t at = off[slot];
       // (always true, by the scan: nothing is stored outside the batch's cells, nor outside the block's range of them)
       if (at >= block_base && at + s.size <= block_end && at + s.size <= cells_bytes && s.size < ((uint64_t)1 << 32)) {
-        const ImpLine L = imp_line_of(B, line);
         const int64_t row = S.row[j];
         ImpSink<true> o;
         o.out = staged ? s_stage + (at - block_base) + pad : cells + at;
         o.base = at; o.def = def; o.ndef = ndef; o.def_cap = def_cap; o.line = line;
-        const uint32_t e = imp_write(T, L, S.file_idx[j], row, s, o);
+        const uint32_t e = from.write(T, line, S.file_idx[j], row, s, o);
         if (e) imp_raise(err, e, line);
         key = imp_sort_key(T, s.col, row);
         src = (uint64_t)(uintptr_t)(cells + at);
@@ -321,6 +364,12 @@ struct DeviceImporter::Impl {
   BgzfDeviceInflater inflater;
   DBuf<char> d_win[2];               // the window and the one the carried partial line moves to
   DBuf<unsigned long long> d_find;
+  // BCF2 input: the file's tables, and per batch the record offsets and the index pass's tables
+  DBuf<int32_t> d_dict_info, d_dict_fmt, d_dict_filter;
+  DBuf<int64_t> d_contig_off;
+  DBuf<uint32_t> d_rec_off;
+  DBuf<ImpBcfRec> d_rec;
+  DBuf<ImpBcfField> d_fld;
 
   ImpTables tables(int n_samples) const {
     ImpTables T = H.view(opt, n_samples);
@@ -342,6 +391,16 @@ struct DeviceImporter::Impl {
   int upload_samples(const ImportHeader& hdr);                              // -> imported samples of the file
   void append_text(const ImportFile& file, const std::string& text);        // inflated text of a whole file, on the host
   void append_bgzf(const ImportFile& file, const std::string& raw, const std::vector<BgzfMember>& mem);
+  void append_bcf(const ImportFile& file, const char* data, size_t n);      // a whole BCF2 stream, inflated
+  const ImportFile& file_named(const std::string& filename) const;
+  // measure, layout and write of the n_lines x max(n_imp, 1) slots of a batch whose index pass is queued (ev[0], ev[1] recorded).
+  // host_text: the batch's text for the deferred tokens; describe(bit, line) / where(line): the words of an error
+  struct BatchWords {
+    std::function<const char*()> host_text; size_t n_text = 0;
+    std::function<std::string(uint32_t, uint32_t)> describe;
+    std::function<std::string(uint32_t)> where;
+  };
+  template <class Src> void cells_of_batch(const Src& src, const ImpTables& T, uint32_t n_lines, int n_imp, const BatchWords& words);
   void find_newlines(const char* text, uint64_t lo, uint64_t mid, uint64_t hi, uint64_t* last_below, uint64_t* first_above);
 };
 
@@ -400,7 +459,19 @@ DeviceImporter::~DeviceImporter() {
 
 const ImportStats& DeviceImporter::stats() const { return m_->st; }
 
-void DeviceImporter::import_all() { for (const ImportFile& f : m_->files) append_file(f.name); }
+void DeviceImporter::import_all(const std::vector<ImportStream>& streams) {
+  for (const ImportStream& s : streams) {
+    bool used = false;
+    for (const ImportFile& f : m_->files) used = used || f.name == s.name;
+    if (!used) throw VCF2BinaryException("stream " + s.name + " is not a \"filename\" of the callset mapping");
+  }
+  for (const ImportFile& f : m_->files) {
+    const ImportStream* from = nullptr;
+    for (const ImportStream& s : streams) if (s.name == f.name) from = &s;
+    if (from) append_buffer(f.name, from->data, from->nbytes);
+    else append_file(f.name);
+  }
+}
 
 namespace {
 uint64_t file_bytes(const std::string& path) { struct stat sb; return stat(path.c_str(), &sb) == 0 ? (uint64_t)sb.st_size : 0u; }
@@ -429,10 +500,21 @@ void inflate_member_host(const std::string& raw, const BgzfMember& m, std::strin
 void DeviceImporter::append_file(const std::string& filename) {
   Impl& M = *m_;
   IMP_HIP_CHECK(hipSetDevice(M.device));
-  const ImportFile* file = nullptr;
-  for (const ImportFile& f : M.files) if (f.name == filename) file = &f;
-  if (!file) throw VCF2BinaryException("file " + filename + " is not in the callset mapping");
+  const ImportFile* file = &M.file_named(filename);
   const double t0 = now_s();
+  if (file_is_bcf2(file->path)) {       // the content decides, plain or compressed; BCF2 records cross BGZF members, so the host inflates
+    if (M.inflate_mode == kInflateDevice)
+      throw VCF2BinaryException(file->path + " is BCF2: BCF2 input is inflated on the host in this build, and inflating on the device was required");
+    std::string data;
+    try { data = gz_text::read_all(file->path); }
+    catch (const std::exception&) { throw VCF2BinaryException("cannot read " + file->path); }
+    M.st.s_read += now_s() - t0;
+    M.st.compressed_bytes += file_bytes(file->path);
+    ++M.st.num_files;
+    ++M.st.num_host_inflated_files;
+    M.append_bcf(*file, data.data(), data.size());
+    return;
+  }
   std::string raw;
   std::vector<BgzfMember> mem;
   bool is_bgzf = false;
@@ -673,21 +755,35 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
                      n_lines, n_tabs);
   IMP_HIP_CHECK(hipEventRecord(ev[1], stream));
 
+  const ImpTables T = tables(hdr.n_samples);
+  BatchWords words;
+  words.host_text = host_text; words.n_text = n_text;
+  words.where = [&](uint32_t line) { return file.path + " line " + std::to_string(lines_before + (int64_t)line + 1); };
+  words.describe = [&](uint32_t bit, uint32_t line) {
+    uint32_t lb = 0, le = 0;
+    if (line) { IMP_HIP_CHECK(hipMemcpy(&lb, d_nl.p + (line - 1), sizeof(uint32_t), hipMemcpyDeviceToHost)); ++lb; }
+    IMP_HIP_CHECK(hipMemcpy(&le, d_nl.p + line, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    le = std::min<uint32_t>(le, (uint32_t)n_text);
+    return describe_line_error(bit, H, opt, hdr, host_text(), lb, le, words.where(line));
+  };
+  cells_of_batch(ImpTextSrc{ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}}, T, n_lines, n_imp, words);
+  return n_lines;
+}
+
+template <class Src> void DeviceImporter::Impl::cells_of_batch(const Src& src, const ImpTables& T, uint32_t n_lines, int n_imp, const BatchWords& words) {
   // ---- measure
   if (spanning && seq_bits < 64 && ((line_seq + n_lines + 1) >> seq_bits) != 0)
     throw VCF2BinaryException("too many record lines for the partition-begin rule of the device importer at column_begin " + std::to_string(opt.column_begin));
   const uint64_t n_slots = (uint64_t)n_lines * (uint64_t)std::max(n_imp, 1);
   if (total_slots + n_slots >= ((uint64_t)1 << 32)) throw VCF2BinaryException("more than 2^32 (record line, sample) pairs in one device import: split the callset mapping");
   d_col.ensure(n_slots); d_end.ensure(n_slots); d_size.ensure(n_slots + 1); d_off.ensure(n_slots + 1); d_kind.ensure(n_slots);
-  const ImpTables T = tables(hdr.n_samples);
-  const ImpBatch B{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines};
   const ImpSamples S{d_samp_idx.p, d_samp_row.p, n_imp};
   const ImpSpan P{spanning ? d_row_best.p : nullptr, seq_bits, line_seq, H.max_row};
   IMP_HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(uint32_t), stream));
   IMP_HIP_CHECK(hipMemsetAsync(d_err.p + 1, 0xFF, (kErrWords - 1) * sizeof(uint32_t), stream));
   IMP_HIP_CHECK(hipMemsetAsync(d_counters.p, 0, 2 * sizeof(unsigned long long), stream));
   IMP_HIP_CHECK(hipMemsetAsync(d_size.p + n_slots, 0, sizeof(uint64_t), stream));
-  hipLaunchKernelGGL(k_imp_measure, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, B, S, P, n_slots, d_col.p, d_end.p, d_size.p, d_kind.p, d_err.p, d_counters.p);
+  hipLaunchKernelGGL(k_imp_measure<Src>, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, src, S, P, n_slots, d_col.p, d_end.p, d_size.p, d_kind.p, d_err.p, d_counters.p);
   IMP_HIP_CHECK(hipEventRecord(ev[2], stream));
   scan<uint64_t>(d_size.p, d_off.p, (size_t)n_slots + 1);
   uint64_t cells_bytes = 0;
@@ -710,11 +806,11 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
     IMP_HIP_CHECK(hipMemsetAsync(d_ndef.p, 0, sizeof(uint32_t), stream));
     IMP_HIP_CHECK(hipEventRecord(ev[3], stream));
     if (stage_in_lds)
-      hipLaunchKernelGGL(k_imp_write<true>, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, B, S, P, n_slots, (const int64_t*)d_col.p, (const int64_t*)d_end.p,
+      hipLaunchKernelGGL((k_imp_write<true, Src>), dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, src, S, P, n_slots, (const int64_t*)d_col.p, (const int64_t*)d_end.p,
                          (const uint64_t*)d_size.p, (const uint8_t*)d_kind.p, (const uint64_t*)d_off.p, b.cells, cells_bytes, d_def.p, d_ndef.p, (uint32_t)d_def.cap,
                          b.key, b.src, b.size, b.tag, d_err.p);
     else
-      hipLaunchKernelGGL(k_imp_write<false>, dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, B, S, P, n_slots, (const int64_t*)d_col.p, (const int64_t*)d_end.p,
+      hipLaunchKernelGGL((k_imp_write<false, Src>), dim3(grid_for(n_slots)), dim3(kBlock), 0, stream, T, src, S, P, n_slots, (const int64_t*)d_col.p, (const int64_t*)d_end.p,
                          (const uint64_t*)d_size.p, (const uint8_t*)d_kind.p, (const uint64_t*)d_off.p, b.cells, cells_bytes, d_def.p, d_ndef.p, (uint32_t)d_def.cap,
                          b.key, b.src, b.size, b.tag, d_err.p);
     IMP_HIP_CHECK(hipEventRecord(ev[4], stream));
@@ -731,7 +827,7 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[3], ev[4])); st.ms_write += ms;
 
   // ---- deferred tokens: the host importer's parsers, on exactly those tokens
-  t0 = now_s();
+  const double t0 = now_s();
   std::vector<ImpDeferred> def(ndef);
   if (ndef) IMP_HIP_CHECK(hipMemcpy(def.data(), d_def.p, (size_t)ndef * sizeof(ImpDeferred), hipMemcpyDeviceToHost));
   std::vector<uint64_t> patch_at(ndef);
@@ -740,9 +836,9 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   std::string bad_text;
   for (uint32_t i = 0; i < ndef; ++i) {
     const ImpDeferred& d = def[i];
-    if ((uint64_t)d.tok_off + d.tok_len > n_text) throw GenomicsDBDeviceException("deferred token outside the batch");
+    if ((uint64_t)d.tok_off + d.tok_len > words.n_text) throw GenomicsDBDeviceException("deferred token outside the batch");
     patch_at[i] = d.out_off;
-    try { patch_val[i] = resolve_deferred(d, host_text(), H); }
+    try { patch_val[i] = resolve_deferred(d, words.host_text(), H); }
     catch (const VCF2BinaryException& e) {
       if (d.line < bad_line) { bad_line = d.line; bad_text = e.what(); bad_text = bad_text.substr(strlen("VCF2BinaryException : ")); }
     }
@@ -751,16 +847,8 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   uint32_t err_line = UINT32_MAX, err_bit = 0;
   for (int k = 0; k < kErrWords - 1; ++k) if ((err[0] & (1u << k)) && err[1 + k] < err_line) { err_line = err[1 + k]; err_bit = 1u << k; }
   if (err_bit || bad_line != UINT32_MAX) {
-    const uint32_t line = std::min(err_line, bad_line);
-    const std::string where = file.path + " line " + std::to_string(lines_before + (int64_t)line + 1);
-    if (err_line <= bad_line) {
-      uint32_t lb = 0, le = 0;
-      if (line) { IMP_HIP_CHECK(hipMemcpy(&lb, d_nl.p + (line - 1), sizeof(uint32_t), hipMemcpyDeviceToHost)); ++lb; }
-      IMP_HIP_CHECK(hipMemcpy(&le, d_nl.p + line, sizeof(uint32_t), hipMemcpyDeviceToHost));
-      le = std::min<uint32_t>(le, (uint32_t)n_text);
-      throw VCF2BinaryException(describe_line_error(err_bit, H, opt, hdr, host_text(), lb, le, where));
-    }
-    throw VCF2BinaryException(bad_text + " (" + where + ")");
+    if (err_line <= bad_line) throw VCF2BinaryException(words.describe(err_bit, err_line));
+    throw VCF2BinaryException(bad_text + " (" + words.where(bad_line) + ")");
   }
   if (ndef) {
     d_patch_at.ensure(ndef); d_patch_val.ensure(ndef);
@@ -775,7 +863,102 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   total_cells += counters[1];
   total_slots += n_slots;
   line_seq += n_lines;
-  return n_lines;
+}
+
+void DeviceImporter::Impl::append_bcf(const ImportFile& file, const char* data, size_t n) {
+  const BcfHeaderHost hdr = parse_bcf_header(data, n, file, H);
+  const int n_imp = upload_samples(hdr.samples);
+  auto up = [&](auto& buf, const auto& v) {
+    buf.ensure(std::max<size_t>(v.size(), 1));
+    if (!v.empty()) IMP_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, stream));
+  };
+  up(d_dict_info, hdr.dict_info); up(d_dict_fmt, hdr.dict_fmt); up(d_dict_filter, hdr.dict_filter); up(d_contig_off, hdr.contig_off);
+  IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  ImpBcfTables BT = hdr.view();
+  BT.dict_info = d_dict_info.p; BT.dict_fmt = d_dict_fmt.p; BT.dict_filter = d_dict_filter.p; BT.contig_off = d_contig_off.p;
+  const ImpTables T = tables(hdr.samples.n_samples);
+  const uint32_t n_attr = (uint32_t)(H.info.size() + H.fmt.size());
+  // the host walks the chain (8 bytes per record) and cuts batches at record boundaries
+  std::vector<uint64_t> offs;
+  bcf_walk_records(data, n, hdr.records_begin, file.path, offs);
+  std::vector<uint32_t> rel;
+  for (size_t first = 0; first + 1 < offs.size();) {
+    const size_t last = bcf_next_batch(offs, first, budget);
+    const uint64_t base = offs[first], n_bytes = offs[last] - base;
+    if (n_bytes >= ((uint64_t)1 << 31)) throw VCF2BinaryException("a BCF2 record of 2 GiB or more in " + file.path);
+    const uint32_t n_rec = (uint32_t)(last - first);
+    rel.resize((size_t)n_rec + 1);
+    for (size_t k = 0; k <= n_rec; ++k) rel[k] = (uint32_t)(offs[first + k] - base);
+    ++st.num_batches;
+    st.text_bytes += n_bytes;
+    const double t0 = now_s();
+    d_text.ensure((size_t)n_bytes + kTextPad);
+    d_rec_off.ensure((size_t)n_rec + 1);
+    d_rec.ensure(n_rec);
+    d_fld.ensure(std::max<size_t>((size_t)n_rec * n_attr, 1));
+    IMP_HIP_CHECK(hipMemcpyAsync(d_text.p, data + base, (size_t)n_bytes, hipMemcpyHostToDevice, stream));
+    IMP_HIP_CHECK(hipMemcpyAsync(d_rec_off.p, rel.data(), rel.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
+    st.bytes_h2d += n_bytes + rel.size() * sizeof(uint32_t);
+    st.s_h2d += now_s() - t0;
+    // ---- index: one thread per record
+    IMP_HIP_CHECK(hipEventRecord(ev[0], stream));
+    hipLaunchKernelGGL(k_imp_bcf_index, dim3(grid_for(n_rec)), dim3(kBlock), 0, stream, T, BT, (const uint8_t*)d_text.p, (uint32_t)n_bytes, (const uint32_t*)d_rec_off.p, n_rec,
+                       d_rec.p, d_fld.p, n_attr);
+    IMP_HIP_CHECK(hipEventRecord(ev[1], stream));
+    BatchWords words;
+    words.host_text = []() -> const char* { return nullptr; };      // (nothing is deferred)
+    words.where = [&](uint32_t r) { return file.path + " record " + std::to_string(first + r + 1); };
+    words.describe = [&](uint32_t bit, uint32_t r) {
+      return describe_bcf_error(bit, H, opt, hdr, (const uint8_t*)data + base, rel[r], rel[r + 1u], words.where(r));
+    };
+    cells_of_batch(ImpBcfSrc{BT, (const uint8_t*)d_text.p, d_rec.p, d_fld.p, n_attr}, T, n_rec, n_imp, words);
+    first = last;
+  }
+}
+
+const ImportFile& DeviceImporter::Impl::file_named(const std::string& filename) const {
+  for (const ImportFile& f : files) if (f.name == filename) return f;
+  throw VCF2BinaryException("file " + filename + " is not in the callset mapping");
+}
+
+void DeviceImporter::append_buffer(const std::string& name, const void* ptr, uint64_t nbytes) {
+  Impl& M = *m_;
+  IMP_HIP_CHECK(hipSetDevice(M.device));
+  ImportFile file = M.file_named(name);
+  file.path = name;       // messages name the stream
+  if (!ptr && nbytes) throw VCF2BinaryException("stream " + name + ": null data");
+  const char* data = (const char*)ptr;
+  const double t0 = now_s();
+  std::string inflated;
+  const bool gz = is_gzip(data, (size_t)nbytes);
+  if (gz) {
+    // a BGZF stream of VCF text may still be inflated on the device; BCF2 records cross members, so BCF2 is inflated here
+    std::vector<BgzfMember> mem;
+    if (M.inflate_mode != kInflateHost && nbytes >= 18 && bgzf_begins((const uint8_t*)data) && bgzf_walk((const uint8_t*)data, (size_t)nbytes, mem, nullptr)) {
+      const std::string first = inflate_gzip_buffer(data, mem.size() > 1 ? (size_t)mem[1].offset : (size_t)nbytes, name);
+      if (!is_bcf2(first.data(), first.size())) {
+        M.st.s_read += now_s() - t0;
+        M.st.compressed_bytes += nbytes;
+        ++M.st.num_files;
+        M.append_bgzf(file, std::string(data, (size_t)nbytes), mem);
+        return;
+      }
+    }
+    inflated = inflate_gzip_buffer(data, (size_t)nbytes, name);
+    data = inflated.data();
+  }
+  const size_t n = gz ? inflated.size() : (size_t)nbytes;
+  const bool bcf = is_bcf2(data, n);
+  if (M.inflate_mode == kInflateDevice)
+    throw VCF2BinaryException(bcf ? name + " is BCF2: BCF2 input is inflated on the host in this build, and inflating on the device was required"
+                                  : name + " is not a BGZF file from its first byte to its last, and inflating on the device was required");
+  M.st.s_read += now_s() - t0;
+  M.st.compressed_bytes += nbytes;
+  ++M.st.num_files;
+  ++M.st.num_host_inflated_files;
+  if (bcf) M.append_bcf(file, data, n);
+  else M.append_text(file, gz ? inflated : std::string(data, n));
 }
 
 void DeviceImporter::finish(std::vector<uint8_t>& cells) {
@@ -843,10 +1026,10 @@ void DeviceImporter::finish(std::vector<uint8_t>& cells) {
 }
 
 std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes, ImportStats* stats,
-                                                     int inflate_mode) {
+                                                     int inflate_mode, const std::vector<ImportStream>& streams) {
   const double t0 = now_s();
   DeviceImporter imp(device, vid, opt, text_budget_bytes, inflate_mode);
-  imp.import_all();
+  imp.import_all(streams);
   std::vector<uint8_t> out;
   imp.finish(out);
   if (stats) { *stats = imp.stats(); stats->s_total = now_s() - t0; }

@@ -7,7 +7,8 @@
 //                                    to stdout, like the reference loader's in-line BroadCombinedGVCFOperator
 // --import-on-device: the conversion runs on the rank's GPU (LOCAL_RANK / GDBAMD_DEVICE, as the other tools choose it) and gives the
 // same cells; the default is the host importer.  On the device, bgzip'ed input (BGZF) is inflated there too and crosses the link
-// compressed; --inflate-on-host keeps zlib on the host for every file.
+// compressed; --inflate-on-host keeps zlib on the host for every file.  BCF2 files (.bcf, sniffed by content) are read with
+// --import-on-device only; without it the tool names the file and exits with an error.
 // The --split-files modes of the reference tool are not implemented (exit with an error).
 #include <getopt.h>
 #include <sys/stat.h>

@@ -275,6 +275,22 @@ int gdbamd_import_cells_device(const char* vid_mapping_file, const char* callset
 int gdbamd_import_cells_device_ex(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                                   int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device, uint64_t text_budget_bytes,
                                   int inflate_mode, double* stats, int nstats);
+/* BCF2 input.  The device calls above sniff every file's content, not its name: input whose (inflated) bytes begin with 'BCF\2\1' or 'BCF\2\2'
+ * is BCF2 - plain (bcftools -Ou, an htsjdk BCF stream) or BGZF / gzip (the usual .bcf) - and gives the cells of the same records written as VCF
+ * text; one callset mapping may mix VCF and BCF2 files.  Compressed BCF2 is inflated on the host (inflate_mode 2 refuses it with an error that
+ * says so); nothing of a BCF2 file is deferred, and stats slot 7 counts its record bytes.  The host walks the record chain and names file,
+ * 1-based record number and byte offset of a broken one; the device refuses, with file and record number, an unknown type code, a vector that
+ * runs past its block, a dictionary or contig id outside the header's range and an n_sample other than the header's.  Float or char values for
+ * an integer attribute of the vid are an error that names the field; integers for a float attribute are converted.
+ * gdbamd_import_cells (the host importer) refuses a BCF2 file by name.
+ *
+ * Buffer streams (the reference's jniAddBufferStream / VCFBufferReader): a callset whose "filename" equals names[i] is read from the nbytes[i]
+ * bytes at data[i] instead of a file - VCF text or BCF2, plain or gzip, sniffed like a file's content.  A name that no callset uses is an
+ * error; a callset without a stream is read from its file as before.  nstreams 0 is gdbamd_import_cells_device_ex. */
+int gdbamd_import_cells_device_streams(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                                       int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device,
+                                       uint64_t text_budget_bytes, int inflate_mode, double* stats, int nstats, int nstreams, const char* const* names,
+                                       const void* const* data, const uint64_t* stream_nbytes);
 void gdbamd_free(void* p);
 
 #ifdef __cplusplus
