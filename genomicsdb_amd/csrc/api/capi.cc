@@ -279,7 +279,7 @@ static void fill_interval_stats(gdbamd_interval_stats* out, const IntervalStats&
   out->num_record_types = s.num_record_types; out->resolved_entry_bytes = s.resolved_entry_bytes;
   out->num_text_slots = s.num_text_slots; out->text_pool_bytes = s.text_pool_bytes;
   out->num_remap_elements = s.num_remap_elements;
-  out->bytes_compressed = s.bytes_compressed; out->ms_compress = s.ms_compress; out->reserved1 = 0;
+  out->bytes_compressed = s.bytes_compressed; out->ms_compress = s.ms_compress; out->page_kernel = s.page_kernel;
   for (int i = 0; i < GDBAMD_GT_NUM_STATS; ++i) out->gt_profile_stats[i] = s.gt_profile[i];
 }
 int gdbamd_engine_run_interval(void* e, int64_t qb, int64_t qe, uint64_t arena_bytes, char* host_out, uint64_t host_cap, uint64_t* host_len,

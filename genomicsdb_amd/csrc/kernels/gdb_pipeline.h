@@ -41,6 +41,7 @@ struct IntervalStats {
   uint64_t num_remap_elements = 0; // sum over re-indexed records of (calls with PL) x (merged genotypes)
   uint64_t bytes_compressed = 0;   // BGZF output formats: bytes of the pages after compression (bytes_out stays the uncompressed size)
   float ms_compress = 0;           // device time of the compression kernels
+  int page_kernel = 0;             // digits S K W C II of the most recent page launch (see include/genomicsdb_amd.h), set at the launch sites; 0: no page yet
   // the reference's GTProfileStats counters (query_variants.h:67-124), per interval; see include/genomicsdb_amd.h
   uint64_t gt_profile[6] = {0, 0, 0, 0, 0, 0};
 };

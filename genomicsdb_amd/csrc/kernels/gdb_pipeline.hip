@@ -3881,6 +3881,7 @@ struct DevicePipeline::Impl {
     bool resolved_whole = false, piece_path = false, res_compact = false; int asm_path = 0, NT = 0; int64_t P_rows = 0;
     bool bcf = false; int bcf_F = 0; BcfLayout lay{nullptr, nullptr, nullptr, nullptr};
     bool events = false; int evrun = 0; EventBuf eb{nullptr, nullptr, nullptr, 0};
+    int size_kernel = 0;          // the S digit of IntervalStats::page_kernel: the sizing kernel prepare_interval launched
   } iv;
 
   void* temp_storage(size_t bytes) { temp.ensure(bytes + 256); return temp.p; }
@@ -5450,14 +5451,21 @@ std::string DevicePipeline::variants_text(int64_t qb, int64_t qe, bool with_inte
 uint64_t DevicePipeline::variants_text_bytes() const { return m_->variants_bytes; }
 
 // the sizing / resolution pass of `n` records in `order` (piece-wise kernel by default; GDBAMD_SIZE3=0: the record-by-record one).
-// size_slots: elements of chunk_size (the check mode compares them all)
-static void launch_assemble_size(DevicePipeline::Impl& S, hipStream_t st, dim3 grid, const AsmCtx& ac, const int32_t* order, int64_t n, int32_t N, int nchunks, int run,
+// size_slots: elements of chunk_size (the check mode compares them all).  Returns the kernel it launched as the S digit of
+// IntervalStats::page_kernel; page_kernel_code() puts the digits together at the launch sites.
+enum { kSizeKernelPlain = 0, kSizeKernel3x8 = 1, kSizeKernel3x16 = 2, kSizeKernelPieces = 3, kSizeKernelEvents = 4 };
+enum { kPageKernelWrite = 1, kPageKernelWrite2 = 2, kPageKernelWrite3 = 3, kPageKernelEvents = 4, kPageKernelBcf = 5 };
+constexpr int page_kernel_code(int size_kernel, int page_kernel, int waves, int coop_u, int lds_bytes) {
+  return size_kernel * 100000 + page_kernel * 10000 + waves * 1000 + coop_u * 100 + lds_bytes / 1024;
+}
+static int launch_assemble_size(DevicePipeline::Impl& S, hipStream_t st, dim3 grid, const AsmCtx& ac, const int32_t* order, int64_t n, int32_t N, int nchunks, int run,
                                  uint64_t* chunk_size, size_t size_slots, ResMatrix resolved, int64_t resolved_base, int64_t res_rows) {
   const int rounds = size3_rounds();
-  if (rounds == 0 || run > 64 * 1024) { hipLaunchKernelGGL(k_assemble_size, grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows); return; }
+  if (rounds == 0 || run > 64 * 1024) { hipLaunchKernelGGL(k_assemble_size, grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows); return kSizeKernelPlain; }
   if (rounds >= 16) hipLaunchKernelGGL((k_assemble_size3<16>), grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows);
   else hipLaunchKernelGGL((k_assemble_size3<8>), grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows);
-  if (!size3_check()) return;
+  const int launched = rounds >= 16 ? kSizeKernel3x16 : kSizeKernel3x8;
+  if (!size3_check()) return launched;
   const size_t nres = resolved.wide ? (size_t)n * (size_t)nchunks * kAsmRows : 0;     // (the check runs with the wide layout: res_compact_wanted())
   S.chk_count.ensure(1);
   HIP_CHECK(hipMemsetAsync(S.chk_count.p, 0, sizeof(unsigned long long), st));
@@ -5470,6 +5478,7 @@ static void launch_assemble_size(DevicePipeline::Impl& S, hipStream_t st, dim3 g
   if (chunk_size) hipLaunchKernelGGL(k_compare_words, dim3(blocks_for((int64_t)size_slots * 2)), dim3(kBlock), 0, st, (const uint32_t*)chunk_size, (const uint32_t*)S.chk_sizes.p, (int64_t)size_slots * 2, S.chk_count.p);
   const unsigned long long bad = S.read_back(S.chk_count.p);
   if (bad) throw GenomicsDBDeviceException("GDBAMD_SIZE3_CHECK: the piece-wise sizing pass differs from the record-by-record one in " + std::to_string(bad) + " words");
+  return launched;
 }
 
 void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
@@ -5909,6 +5918,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   HIP_CHECK(hipMemsetAsync(S.max_record.p, 0, sizeof(unsigned long long), st));
   BcfLayout lay{nullptr, nullptr, nullptr, nullptr};
   const int bcf_F = std::max(1, pl.n_format);
+  int size_kernel = 0;
   const uint64_t size2_units = (uint64_t)((P + kSizeBlock - 1) / kSizeBlock) * (uint64_t)nchunks;
   if (asm_path != 0 && size2_units >= (1ull << 31)) throw GenomicsDBDeviceException("more than 2^31 (record block, sample chunk) units in one interval: split the query interval");
   const int frun = fill_run_length();
@@ -5917,9 +5927,10 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     // BCF2: resolve the (record, sample) matrix, reduce the entries' summaries to vector length + type per (record, field), size the records
     if (asm_path == 2) {   // (k_size2 for the walkers' starting points; its text sizes mean nothing here)
       hipLaunchKernelGGL(k_size2, dim3((unsigned)size2_units), dim3(kAsmRows), 0, st, pc2, nchunks, S.chunk_size.p);
+      size_kernel = kSizeKernelPieces;
       hipLaunchKernelGGL(k_fill2, dim3(fill_units), dim3(kAsmRows), 0, st, pc2, (const uint2*)S.slot_desc.p, (const int32_t*)S.order.p, P, nchunks, frun, S.resolved.p, (int64_t)0);
     } else
-    launch_assemble_size(S, st, dim3(run_blocks * (unsigned)nchunks), ac, S.order.p, P, N, nchunks, run, (uint64_t*)nullptr, 0, res_view(), (int64_t)0, (int64_t)0);
+    size_kernel = launch_assemble_size(S, st, dim3(run_blocks * (unsigned)nchunks), ac, S.order.p, P, N, nchunks, run, (uint64_t*)nullptr, 0, res_view(), (int64_t)0, (int64_t)0);
     S.bcf_part.ensure(nchunk_total * (size_t)bcf_F + 1); S.bcf_fmeta.ensure((size_t)P * bcf_F + 1); S.bcf_foff.ensure((size_t)P * bcf_F + 1); S.bcf_lindiv.ensure((size_t)P + 1);
     S.bcf_rec_size.ensure((size_t)P + 2);
     lay = BcfLayout{S.bcf_fmeta.p, S.bcf_foff.p, S.bcf_lindiv.p, S.bcf_rec_size.p};
@@ -5940,11 +5951,13 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     S.ev_init.ensure((size_t)ev_blocks * kAsmRows); S.ev_buf.ensure((size_t)ev_blocks * evrun * kAsmRows); S.ev_count.ensure((size_t)ev_blocks);
     ebuf = EventBuf{S.ev_init.p, S.ev_buf.p, S.ev_count.p, evrun};
     hipLaunchKernelGGL(k_assemble_size_ev, dim3((unsigned)ev_blocks), dim3(kAsmRows), 0, st, ac, S.order.p, P, N, nchunks, evrun, S.chunk_size.p, ebuf, S.err.p);
+    size_kernel = kSizeKernelEvents;
     S.order_iv.ensure((size_t)P);
     HIP_CHECK(hipMemcpyAsync(S.order_iv.p, S.order.p, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     S.order_iv_valid = true;
   } else if (asm_path != 0) {
     hipLaunchKernelGGL(k_size2, dim3((unsigned)size2_units), dim3(kAsmRows), 0, st, pc2, nchunks, S.chunk_size.p);
+    size_kernel = kSizeKernelPieces;
     if (asm_path == 3) {   // piece lists: count, offsets, fill
       const size_t nlists = (size_t)((P + kSizeBlock - 1) / kSizeBlock) * (size_t)ntypes * (size_t)N;
       S.pl_cnt.ensure(nlists + 1); S.pl_ofs.ensure(nlists + 1);
@@ -5959,7 +5972,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     if (asm_path == 2 && resolved_whole)
       hipLaunchKernelGGL(k_fill2, dim3(fill_units), dim3(kAsmRows), 0, st, pc2, (const uint2*)S.slot_desc.p, (const int32_t*)S.order.p, P, nchunks, frun, S.resolved.p, (int64_t)0);
   } else
-  launch_assemble_size(S, st, dim3(run_blocks * (unsigned)nchunks), ac, S.order.p, P, N, nchunks, run, S.chunk_size.p, nchunk_total, resolved_whole ? res_view() : ResMatrix{nullptr, nullptr, nullptr}, (int64_t)0, res_chunk_major() ? P : (int64_t)0);
+  size_kernel = launch_assemble_size(S, st, dim3(run_blocks * (unsigned)nchunks), ac, S.order.p, P, N, nchunks, run, S.chunk_size.p, nchunk_total, resolved_whole ? res_view() : ResMatrix{nullptr, nullptr, nullptr}, (int64_t)0, res_chunk_major() ? P : (int64_t)0);
   HIP_CHECK(hipMemsetAsync(S.chunk_size.p + nchunk_total, 0, sizeof(uint64_t), st));
   S.excl_scan(S.chunk_size.p, S.chunk_off.p, nchunk_total + 1);
   STAGE("k_gather_record_offsets");
@@ -5984,6 +5997,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   S.iv.sx = sx; S.iv.ex = ex; S.iv.ri = ri; S.iv.so = so; S.iv.rec = rec; S.iv.ac = ac; S.iv.pc2 = pc2; S.iv.piece_path = piece_path; S.iv.asm_path = asm_path; S.iv.resolved_whole = resolved_whole; S.iv.res_compact = res_compact; S.iv.P_rows = P;
   S.iv.bcf = pl.bcf_mode != 0; S.iv.bcf_F = bcf_F; S.iv.lay = lay;
   S.iv.events = use_events; S.iv.evrun = ebuf.run; S.iv.eb = ebuf;
+  S.iv.size_kernel = size_kernel;
   S.iv.active = true;
 }
 
@@ -6059,6 +6073,7 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
     if (S.hp.plan.n_format > 0 && !S.hp.plan.sites_only_query)
       hipLaunchKernelGGL(k_bcf_write, dim3((unsigned)(((np + kBcfRun - 1) / kBcfRun) * iv.nchunks)), dim3(kAsmRows), 0, st_w, S.hp.plan, iv.res_compact ? ResMatrix{nullptr, S.res_off.p, S.res_len8.p} : ResMatrix{S.resolved.p, nullptr, nullptr}, (const char*)S.pool.p,
                          (const char*)S.pool_ovf.p, (const uint32_t*)S.fmt_mask.p, (const int32_t*)S.order.p, (const uint8_t*)S.bcf_same.p, np, iv.nchunks, iv.bcf_F, N, iv.lay, (const uint64_t*)S.rec_off.p, page_base, arena BCF_PROF_ARG);
+    iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelBcf, 1, 0, 0);
 #ifdef GDB_BCF_PROF
     { unsigned long long h[12]; HIP_CHECK(hipStreamSynchronize(st_w)); HIP_CHECK(hipMemcpy(h, bcf_prof_buffer(), sizeof h, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemset(bcf_prof_buffer(), 0, sizeof h));
       fprintf(stderr, "k_bcf_write cycles per step (100 MHz ticks x wavefronts / steps): top %.1f layout %.1f lanes-pass %.1f groups %.1f flush %.1f slow %.1f; steps %llu, with group passes %llu\n", (double)h[0] / h[8], (double)h[1] / h[8],
@@ -6084,12 +6099,15 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
       const unsigned eruns = (unsigned)((np + evrun - 1) / evrun);
       HIP_CHECK(hipEventRecord(w[1], st));
       const unsigned units = eruns * (unsigned)iv.nchunks;
-      if (write_waves_per_group() >= 4)
+      if (write_waves_per_group() >= 4) {
+        iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelEvents, 4, 0, kWaveLds);
         hipLaunchKernelGGL(k_assemble_write_ev<4>, dim3((units + 3u) / 4u), dim3(kAsmRows * 4), 0, st, (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const uint32_t*)S.prefix_len.p,
                            iv.eb, (int64_t)(kp / evrun) * iv.nchunks, (const int32_t*)(S.order_iv.p + kp), np, iv.nchunks, evrun, (const uint64_t*)S.chunk_off.p, page_base, arena);
-      else
+      } else {
+        iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelEvents, 1, 0, kWaveLds);
         hipLaunchKernelGGL(k_assemble_write_ev<1>, dim3(units), dim3(kAsmRows), 0, st, (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const uint32_t*)S.prefix_len.p,
                            iv.eb, (int64_t)(kp / evrun) * iv.nchunks, (const int32_t*)(S.order_iv.p + kp), np, iv.nchunks, evrun, (const uint64_t*)S.chunk_off.p, page_base, arena);
+      }
       HIP_CHECK(hipEventRecord(w[2], st));
       HIP_CHECK(hipMemcpyAsync(&S.hb->page_err[ai], S.err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipEventRecord(w[3], st));
@@ -6104,14 +6122,14 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
   const dim3 wgrid(wruns * (unsigned)iv.nchunks);
   if (iv.piece_path) {
     HIP_CHECK(hipEventRecord(w[1], st));
-#define GDB_LAUNCH_WRITE2(W, L) hipLaunchKernelGGL((k_write2<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st, iv.pc2, (const char*)S.pool.p, (const char*)S.pool_ovf.p, \
-    (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, (xcd_aware_numbering() ? 1 : 0) | (w2dbg << 1))
+#define GDB_LAUNCH_WRITE2(W, L) do { iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite2, W, 0, L); hipLaunchKernelGGL((k_write2<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st, iv.pc2, (const char*)S.pool.p, (const char*)S.pool_ovf.p, \
+    (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, (xcd_aware_numbering() ? 1 : 0) | (w2dbg << 1)); } while (0)
     const int ww = write_waves_per_group(), wl = write_image_kb(iv.P > 0 && iv.nchunks > 0 ? iv.total_bytes / ((uint64_t)iv.P * (uint64_t)iv.nchunks) : 0);
     const int w2dbg = getenv("GDBAMD_W2_DBG") ? atoi(getenv("GDBAMD_W2_DBG")) : 0;
     S.dbg_counters.ensure(8);
     if (w2dbg & 64) HIP_CHECK(hipMemsetAsync(S.dbg_counters.p, 0, 8 * sizeof(unsigned long long), st));
-#define GDB_LAUNCH_WRITE3(W, L) hipLaunchKernelGGL((k_write3<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st, iv.pc2, (const PieceEntry*)S.plist.p, (const uint32_t*)S.pl_ofs.p, iv.NT, \
-    (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, (xcd_aware_numbering() ? 1 : 0) | (w2dbg << 1), S.dbg_counters.p)
+#define GDB_LAUNCH_WRITE3(W, L) do { iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite3, W, 0, L); hipLaunchKernelGGL((k_write3<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st, iv.pc2, (const PieceEntry*)S.plist.p, (const uint32_t*)S.pl_ofs.p, iv.NT, \
+    (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, (xcd_aware_numbering() ? 1 : 0) | (w2dbg << 1), S.dbg_counters.p); } while (0)
     if (iv.asm_path == 3) { if (wl <= 4) GDB_LAUNCH_WRITE3(1, 4096); else GDB_LAUNCH_WRITE3(1, 8192); }
     else
     if (ww >= 4 && wl <= 4) GDB_LAUNCH_WRITE2(4, 4096);
@@ -6148,14 +6166,15 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
   }
   const hipStream_t st_w = fork_page_stream();
   HIP_CHECK(hipEventRecord(w[1], st_w));   // [w1, w2] brackets the page-assembly kernel alone (its duration feeds the roofline figure)
-#define GDB_LAUNCH_WRITE(W, L) hipLaunchKernelGGL((k_assemble_write<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st_w, (const char*)S.pool.p, (const char*)S.pool_ovf.p, \
+#define GDB_LAUNCH_WRITE(W, L) do { iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite, W, 2, L); hipLaunchKernelGGL((k_assemble_write<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st_w, (const char*)S.pool.p, (const char*)S.pool_ovf.p, \
     (const uint32_t*)S.prefix_len.p, res_view(), iv.resolved_whole ? (int64_t)0 : kp, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, xcd_aware_numbering() ? 1 : 0, \
-    (res_chunk_major() && iv.asm_path != 2) ? (iv.resolved_whole ? (int64_t)iv.P_rows : np) : (int64_t)0)
+    (res_chunk_major() && iv.asm_path != 2) ? (iv.resolved_whole ? (int64_t)iv.P_rows : np) : (int64_t)0); } while (0)
   {
     const int ww = write_waves_per_group(), wl = write_image_kb(iv.P > 0 && iv.nchunks > 0 ? iv.total_bytes / ((uint64_t)iv.P * (uint64_t)iv.nchunks) : 0);
     // the largest record's average entry is a long one (copied by the whole wavefront): the variant that keeps 4 words per lane in flight
     const bool long_entries = coop_unroll_wanted() && iv.nchunks > 0 && iv.max_record_bytes / ((uint64_t)iv.nchunks * kAsmRows) > (uint64_t)kCooperativeEntry;
     if (long_entries && ww == 1) {
+      iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite, 1, 4, 8192);
       hipLaunchKernelGGL((k_assemble_write<1, 8192, 4>), dim3(wgrid.x), dim3(kAsmRows), 0, st_w, (const char*)S.pool.p, (const char*)S.pool_ovf.p,
         (const uint32_t*)S.prefix_len.p, res_view(), iv.resolved_whole ? (int64_t)0 : kp, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, xcd_aware_numbering() ? 1 : 0,
         (res_chunk_major() && iv.asm_path != 2) ? (iv.resolved_whole ? (int64_t)iv.P_rows : np) : (int64_t)0);

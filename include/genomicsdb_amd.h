@@ -101,7 +101,12 @@ typedef struct gdbamd_interval_stats {
   int64_t num_text_slots, text_pool_bytes;
   uint64_t num_remap_elements;           /* sum over re-indexed records of (calls with PL) x (merged genotypes): the PL remap work */
   uint64_t bytes_compressed;             /* output formats "z" / "b": bytes of the pages after BGZF compression (bytes_out: before) */
-  float ms_compress; int32_t reserved1;  /* device time of the compression kernels */
+  float ms_compress;                     /* device time of the compression kernels */
+  int32_t page_kernel;                   /* which kernels the interval ran, as the decimal digits S K W C II of its most recent page launch (0: no page was
+                                          * launched).  S = sizing kernel of the interval: 0 k_assemble_size, 1 k_assemble_size3<8>, 2 k_assemble_size3<16>,
+                                          * 3 k_size2, 4 k_assemble_size_ev.  K = page kernel: 1 k_assemble_write, 2 k_write2, 3 k_write3, 4 k_assemble_write_ev,
+                                          * 5 the BCF2 kernels.  W = wavefronts per workgroup, C = 16-byte words per lane in flight in the cooperative copy
+                                          * (0: the kernel has no such parameter), II = LDS image in KiB.  The default text path reads 111204. */
   /* the six counters of the reference's GTProfileStats (src/main/cpp/include/genomicsdb/query_variants.h:67-124, -DDO_PROFILING),
    * indexed by the enum below; counted per interval on the device.  The reference counts cell VISITS of its iterators; here every
    * cell is touched once per interval, so: NUM_CELLS = cells of the staged window considered for the interval, IN_LEFT_SWEEP =

@@ -37,6 +37,70 @@ def bgzf_blocks(data):
     return out
 
 
+# The named hostile inputs of the two deflate kernels, at module level: test_gpu_kernel_variants.py sends the same ones through the
+# non-default block sizes and kernels (GDBAMD_BGZF_BLOCK / _WAVES / _TEXT, read once per process) in child processes.
+def _hostile_inputs():
+    rnd = random.Random(11)
+    return {
+        "empty": b"",
+        "one byte": b"x",
+        "three bytes": b"abc",
+        "zeros": bytes(100_000),                                            # matches of 258 at distance 1 .. (overlapping copies)
+        "one block exactly": bytes(rnd.getrandbits(8) for _ in range(8192)),    # incompressible: stored block
+        "two blocks exactly": bytes(rnd.getrandbits(8) for _ in range(16384)),
+        "one block + 1": b"ab" * 4096 + b"c",
+        "16 KiB + 1": b"ab" * 8192 + b"c",
+        "random": bytes(rnd.getrandbits(8) for _ in range(70_000)),
+        "text": b"".join(b"./.:%d:.:%d:0,%d,%d\t" % (rnd.choice([0, 20, 50, 99]), rnd.randint(10, 60), rnd.randint(1, 300), rnd.randint(1, 4000)) for _ in range(9000)),
+        "period 255": bytes(range(255)) * 300,
+        "long then literal tail": b"q" * 8189 + b"xyz" + b"r" * 8189 + b"uvw",
+        "high bytes": bytes(rnd.choice([200, 250, 255, 144, 143]) for _ in range(40_000)),
+        "all byte values": bytes(range(256)) * 64 + bytes(reversed(range(256))) * 64,
+    }
+
+
+def _hostile_text_inputs():
+    rnd = random.Random(12)
+    def entry():
+        gq = rnd.choice([0, 20, 50, 99])
+        return b"\t./.:%d:.:.:0,%d,%d,%d,%d,%d:%d:%d" % (gq, 3 * gq, 45 * gq, 3 * gq, 45 * gq, 45 * gq, rnd.randint(10, 60), rnd.randint(10, 60))
+    def record(i, nsamples):
+        return b"1\t%d\t.\tA\t<NON_REF>\t.\t.\tEND=%d\tGT:GQ:SB:AD:PL:MIN_DP:DP" % (10_000_000 + i, 10_000_000 + i) + b"".join(entry() for _ in range(nsamples)) + b"\n"
+    return {
+        "empty": b"",
+        "one byte": b"x",
+        "one tab": b"\t",
+        "three bytes": b"a\tc",
+        "zeros": bytes(100_000),
+        "tabs only": b"\t" * 50_000,
+        "newlines and tabs": b"\t\n" * 30_000,
+        "tab every 2": b"\t." * 40_000,
+        "tab every 7": b"\t./.:.:" [:7] * 12_000,
+        "tab every 9": b"\t12345678" * 9_000,
+        "no delimiter at all": bytes(rnd.choice(b"ACGTN") for _ in range(60_000)),
+        "colons only": b":".join(b"%d" % rnd.randint(0, 99999) for _ in range(12_000)),
+        "long columns": b"".join(b"\t" + b",".join(b"%d" % rnd.randint(0, 5000) for _ in range(rnd.randint(1, 120))) for _ in range(800)),
+        "vcf records": b"".join(record(i, 300) for i in range(12)),
+        "vcf records, blocks cut anywhere": b"xy" + b"".join(record(i, 57) for i in range(60)),
+        "one block exactly": bytes(rnd.getrandbits(8) for _ in range(8192)),
+        "random": bytes(rnd.getrandbits(8) for _ in range(70_000)),
+        "random with tabs": bytes(rnd.choice([9, 10, 58, 44]) if rnd.random() < 0.1 else rnd.getrandbits(8) for _ in range(70_000)),
+        "high bytes in columns": b"".join(b"\t" + bytes(rnd.choice([200, 250, 255, 144, 143, 65]) for _ in range(rnd.randint(0, 40))) for _ in range(4_000)),
+        "repeated column": b"\t./.:99:.:.:0,297,4455,297,4455,4455:34:55" * 3_000,
+        "columns of 95+ bytes": (b"\t" + b"q" * 300) * 200,
+        # wide-cohort columns: secondary anchors inside a column continue the anchor in front, the matches merge into one token and
+        # runs are cut where they would pass 258 bytes
+        "long PL columns repeated": b"".join((b"\t./.:99:.:.:" + b",".join(b"%d" % (37 * k % 5000) for k in range(g)) + b":34:55") * 3 for g in (21, 28, 36, 45, 66, 120)) * 40,
+        "long PL columns, one value changed": b"".join(b"\t./.:99:.:.:" + b",".join(b"%d" % ((37 * k + (i == k) * 7) % 5000) for k in range(45)) + b":34:55" for i in range(300)),
+        "period 255": bytes(range(255)) * 300,
+        "8189 + 3": b"q" * 8189 + b"x\tz" + b"r" * 8189 + b"u\tw",
+    }
+
+
+HOSTILE_INPUTS = _hostile_inputs()
+HOSTILE_TEXT_INPUTS = _hostile_text_inputs()
+
+
 def test_host_side_blocks_and_eof_marker():
     """the header goes through zlib on the host; the EOF marker is the one every BGZF file ends with (an empty fixed-Huffman block)"""
     blocks = bgzf_blocks(EOF_BLOCK)
@@ -66,23 +130,7 @@ def _check_roundtrip(gdb, data, vcf_text=False):
 
 @pytest.mark.gpu
 def test_device_deflate_on_hostile_inputs(gdb):
-    rnd = random.Random(11)
-    cases = {
-        "empty": b"",
-        "one byte": b"x",
-        "three bytes": b"abc",
-        "zeros": bytes(100_000),                                            # matches of 258 at distance 1 .. (overlapping copies)
-        "one block exactly": bytes(rnd.getrandbits(8) for _ in range(8192)),    # incompressible: stored block
-        "two blocks exactly": bytes(rnd.getrandbits(8) for _ in range(16384)),
-        "one block + 1": b"ab" * 4096 + b"c",
-        "16 KiB + 1": b"ab" * 8192 + b"c",
-        "random": bytes(rnd.getrandbits(8) for _ in range(70_000)),
-        "text": b"".join(b"./.:%d:.:%d:0,%d,%d\t" % (rnd.choice([0, 20, 50, 99]), rnd.randint(10, 60), rnd.randint(1, 300), rnd.randint(1, 4000)) for _ in range(9000)),
-        "period 255": bytes(range(255)) * 300,
-        "long then literal tail": b"q" * 8189 + b"xyz" + b"r" * 8189 + b"uvw",
-        "high bytes": bytes(rnd.choice([200, 250, 255, 144, 143]) for _ in range(40_000)),
-        "all byte values": bytes(range(256)) * 64 + bytes(reversed(range(256))) * 64,
-    }
+    cases = HOSTILE_INPUTS
     for name, data in cases.items():
         comp, _ = _check_roundtrip(gdb, data)
         if name in ("zeros", "period 255"):     # (every block starts with its own 255 literals: small blocks find less)
@@ -103,41 +151,7 @@ def test_device_deflate_text_kernel_on_hostile_inputs(gdb):
     """the anchored kernel of the "z" stream (k_bgzf_deflate_text: matches begin at tabs / newlines, four wavefronts per block, each a DEFLATE
     block of its own) must give a valid stream for ANY bytes - anchors only decide how much is found: the hostile inputs of the byte-level
     kernel, texts with every anchor density (a tab at every byte ... none at all), high bytes in the literals, blocks cut anywhere"""
-    rnd = random.Random(12)
-    def entry():
-        gq = rnd.choice([0, 20, 50, 99])
-        return b"\t./.:%d:.:.:0,%d,%d,%d,%d,%d:%d:%d" % (gq, 3 * gq, 45 * gq, 3 * gq, 45 * gq, 45 * gq, rnd.randint(10, 60), rnd.randint(10, 60))
-    def record(i, nsamples):
-        return b"1\t%d\t.\tA\t<NON_REF>\t.\t.\tEND=%d\tGT:GQ:SB:AD:PL:MIN_DP:DP" % (10_000_000 + i, 10_000_000 + i) + b"".join(entry() for _ in range(nsamples)) + b"\n"
-    cases = {
-        "empty": b"",
-        "one byte": b"x",
-        "one tab": b"\t",
-        "three bytes": b"a\tc",
-        "zeros": bytes(100_000),
-        "tabs only": b"\t" * 50_000,
-        "newlines and tabs": b"\t\n" * 30_000,
-        "tab every 2": b"\t." * 40_000,
-        "tab every 7": b"\t./.:.:" [:7] * 12_000,
-        "tab every 9": b"\t12345678" * 9_000,
-        "no delimiter at all": bytes(rnd.choice(b"ACGTN") for _ in range(60_000)),
-        "colons only": b":".join(b"%d" % rnd.randint(0, 99999) for _ in range(12_000)),
-        "long columns": b"".join(b"\t" + b",".join(b"%d" % rnd.randint(0, 5000) for _ in range(rnd.randint(1, 120))) for _ in range(800)),
-        "vcf records": b"".join(record(i, 300) for i in range(12)),
-        "vcf records, blocks cut anywhere": b"xy" + b"".join(record(i, 57) for i in range(60)),
-        "one block exactly": bytes(rnd.getrandbits(8) for _ in range(8192)),
-        "random": bytes(rnd.getrandbits(8) for _ in range(70_000)),
-        "random with tabs": bytes(rnd.choice([9, 10, 58, 44]) if rnd.random() < 0.1 else rnd.getrandbits(8) for _ in range(70_000)),
-        "high bytes in columns": b"".join(b"\t" + bytes(rnd.choice([200, 250, 255, 144, 143, 65]) for _ in range(rnd.randint(0, 40))) for _ in range(4_000)),
-        "repeated column": b"\t./.:99:.:.:0,297,4455,297,4455,4455:34:55" * 3_000,
-        "columns of 95+ bytes": (b"\t" + b"q" * 300) * 200,
-        # wide-cohort columns: secondary anchors inside a column continue the anchor in front, the matches merge into one token and
-        # runs are cut where they would pass 258 bytes
-        "long PL columns repeated": b"".join((b"\t./.:99:.:.:" + b",".join(b"%d" % (37 * k % 5000) for k in range(g)) + b":34:55") * 3 for g in (21, 28, 36, 45, 66, 120)) * 40,
-        "long PL columns, one value changed": b"".join(b"\t./.:99:.:.:" + b",".join(b"%d" % ((37 * k + (i == k) * 7) % 5000) for k in range(45)) + b":34:55" for i in range(300)),
-        "period 255": bytes(range(255)) * 300,
-        "8189 + 3": b"q" * 8189 + b"x\tz" + b"r" * 8189 + b"u\tw",
-    }
+    cases = HOSTILE_TEXT_INPUTS
     for name, data in cases.items():
         comp, _ = _check_roundtrip(gdb, data, vcf_text=True)
         if name in ("vcf records", "vcf records, blocks cut anywhere", "repeated column", "long PL columns repeated", "long PL columns, one value changed"):
