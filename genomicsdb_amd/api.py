@@ -372,7 +372,9 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
     BCF2 (device path only): a file whose content - plain, BGZF or gzip - begins with 'BCF\\2\\1' or 'BCF\\2\\2' is imported as BCF2 and
     gives the cells of the same records as VCF text; compressed BCF2 is inflated on the host (inflate="device" refuses it), and the
     host importer refuses a BCF2 file by name.  streams (device path only): {name: bytes} - a callset whose "filename" equals a name is
-    read from those bytes (VCF text or BCF2, plain or gzip) instead of a file; a name that no callset uses is an error."""
+    read from those bytes (VCF text or BCF2, plain or gzip) instead of a file; a name that no callset uses is an error.
+    CSV cell files (device path only): a "filename" that the callset mapping also lists under "sorted_csv_files" / "unsorted_csv_files"
+    is read as the reference loader's CSV input, one line = one cell (csrc/core/gdb_import_csv.hpp); from a file or from streams=."""
     if inflate not in INFLATE_MODES:
         raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
     if streams is not None and device is None:

@@ -131,6 +131,14 @@ def build_hostsim_import_bcf():
     return os.path.join(d, "libhostsim_import_bcf.so"), os.path.join(d, "malformed_bcf")
 
 
+def build_hostsim_import_csv():
+    """CPU harness around the bodies of the device importer's CSV path (core/gdb_import_csv.hpp) and the same source as a
+    stand-alone program built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_import_csv")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_import_csv.so"), os.path.join(d, "hostsim_import_csv_main")
+
+
 def build_hostsim_inflate():
     """CPU harness around the bodies of the BGZF inflater (core/gdb_inflate.hpp; tests only)"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_inflate")])

@@ -32,6 +32,7 @@ enum ImpErr : uint32_t {
   IMP_ERR_SHORT_LINE = 1u, IMP_ERR_CONTIG = 2u, IMP_ERR_FILTER = 4u, IMP_ERR_COUNT = 8u,
   IMP_ERR_COORD_TEXT = 16u,     // POS / END outside the integer fast path: coordinates decide sizes and order, they are not deferred
   IMP_ERR_COORD_RANGE = 32u     // a column that the 64-bit (column, row) sort key cannot hold
+  // 64 .. 2048: ImpBcfErr (gdb_import_bcf.hpp); 4096 .. 65536: ImpCsvErr (gdb_import_csv.hpp)
 };
 
 struct ImpName { uint32_t off, len; int64_t value; };      // contig: value = column offset; field: value = field index
@@ -51,8 +52,8 @@ struct ImpTables {
 struct ImpLine { const char* text; uint32_t begin, end; const uint32_t* tabs; uint32_t ntabs; };   // end: '\r' already cut
 struct ImpTok { uint32_t b, e; GDB_HD uint32_t n() const { return e - b; } };
 
-enum { IMP_KIND_INT = 0, IMP_KIND_FLOAT = 1 };
-enum { IMP_WHAT_QUAL = -1, IMP_WHAT_GT = -2, IMP_WHAT_FMT_BASE = 1 << 16 };   // else: index of the INFO attribute
+enum { IMP_KIND_INT = 0, IMP_KIND_FLOAT = 1, IMP_KIND_CSV_INT = 2, IMP_KIND_CSV_FLOAT = 3 };   // CSV: strtoll(base 0) / strtof over a prefix
+enum { IMP_WHAT_QUAL = -1, IMP_WHAT_GT = -2, IMP_WHAT_FILTER = -3, IMP_WHAT_FMT_BASE = 1 << 16 };   // else: index of the INFO attribute
 struct ImpDeferred {
   uint32_t tok_off, tok_len;         // the token's text (offset in the batch)
   uint64_t out_off;                  // its 4 output bytes (offset in the batch's cell buffer)
@@ -126,7 +127,8 @@ GDB_HD double imp_pow10(int e) {   // 10^e, 0 <= e <= 22: exactly representable
   }
 }
 
-GDB_HD bool imp_parse_float(const char* p, uint32_t n, float* out) {
+// the value as a double: the digits times an exact power of ten, one correctly rounded operation
+GDB_HD bool imp_parse_decimal(const char* p, uint32_t n, double* out) {
   uint32_t i = 0;
   bool neg = false;
   if (n && (p[0] == '+' || p[0] == '-')) { neg = p[0] == '-'; i = 1; }
@@ -172,7 +174,13 @@ GDB_HD bool imp_parse_float(const char* p, uint32_t n, float* out) {
     v = (double)w;
     v = e10 < 0 ? v / imp_pow10(-e10) : v * imp_pow10(e10);
   }
-  *out = (float)(neg ? -v : v);
+  *out = neg ? -v : v;
+  return true;
+}
+GDB_HD bool imp_parse_float(const char* p, uint32_t n, float* out) {
+  double v;
+  if (!imp_parse_decimal(p, n, &v)) return false;
+  *out = (float)v;
   return true;
 }
 

@@ -3,12 +3,13 @@
 // the refusals, the files of the callset mapping, the header / #CHROM rule of host/vcf_importer.cc, the host parse of deferred
 // tokens and the text of an error found on a record line.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
-#include "../core/gdb_import.hpp"
+#include "../core/gdb_import_csv.hpp"
 #include "vcf_importer.h"
 
 namespace genomicsdb_amd {
@@ -86,7 +87,7 @@ inline ImportTablesHost build_import_tables(const VidMapper& vid) {
   return H;
 }
 
-struct ImportFile { std::string name, path; std::vector<const CallSetInfo*> callsets; };
+struct ImportFile { std::string name, path; std::vector<const CallSetInfo*> callsets; GdbFileType type = GDB_FILE_VCF; };
 // callsets grouped by file, in mapping order
 inline std::vector<ImportFile> import_files(const VidMapper& vid, const ImportOptions& opt) {
   std::vector<ImportFile> files;
@@ -98,11 +99,52 @@ inline std::vector<ImportFile> import_files(const VidMapper& vid, const ImportOp
       ImportFile f;
       f.name = cs.m_filename;
       f.path = (cs.m_filename[0] != '/' && !opt.file_root.empty()) ? opt.file_root + "/" + cs.m_filename : cs.m_filename;
+      f.type = vid.get_file_type(cs.m_filename);
       files.push_back(f);
     }
     files[at[cs.m_filename]].callsets.push_back(&cs);
   }
   return files;
+}
+
+// what the CSV bodies (core/gdb_import_csv.hpp) do not cover, refused by name when the mapping has a CSV file
+inline void refuse_for_csv(const VidMapper& vid, const ImportTablesHost& H, const std::vector<ImportFile>& files) {
+  const ImportFile* csv = nullptr;
+  for (const ImportFile& f : files) if (f.type != GDB_FILE_VCF && !csv) csv = &f;
+  if (!csv) return;
+  // the reference's fixed field indices (variant_array_schema.h:44-48) do not account for the ID attribute: it misreads such lines
+  if (H.has_id) throw VCF2BinaryException("field ID: a vid that declares ID is not imported from CSV cell files (" + csv->path + ")");
+  auto check = [&](const gdbimp::ImpAttr& a, const std::string& name) {
+    if (a.elem != GDB_ET_INT && a.elem != GDB_ET_FLOAT && a.elem != GDB_ET_CHAR)
+      throw VCF2BinaryException("field " + name + ": only int, float and char attributes are imported from CSV cell files (" + csv->path + ")");
+    if (a.elem == GDB_ET_CHAR && a.fixed)
+      throw VCF2BinaryException("field " + name + ": fixed-length char attributes are not imported from CSV cell files (" + csv->path + ")");
+  };
+  for (size_t i = 0; i < H.info.size(); ++i) check(H.info[i], H.info_names[i]);
+  for (size_t i = 0; i < H.fmt.size(); ++i) check(H.fmt[i], H.fmt_names[i]);
+}
+// the rows of a CSV file's callsets, ascending and without repeats: the table a line's row is looked up in
+inline std::vector<int64_t> csv_rows_of(const ImportFile& file) {
+  std::vector<int64_t> rows;
+  for (const CallSetInfo* cs : file.callsets) rows.push_back(cs->m_row_idx);
+  std::sort(rows.begin(), rows.end());
+  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  return rows;
+}
+// CSV cell files are opened as they are (the reference uses fopen): compressed content is refused by name
+inline void refuse_compressed_csv(const char* data, size_t n, const std::string& path) {
+  if (n >= 2 && (uint8_t)data[0] == 0x1f && (uint8_t)data[1] == 0x8b)
+    throw VCF2BinaryException(path + " is gzip or BGZF: compressed CSV cell files are not imported");
+}
+// where a batch of text that begins at pos ends: at most `budget` bytes cut behind a newline; a line longer than the budget grows its batch
+inline size_t import_text_cut(const char* text, size_t size, size_t pos, uint64_t budget) {
+  size_t stop = size;
+  if (stop - pos > budget) {
+    const void* nl = memrchr(text + pos, '\n', (size_t)budget);
+    if (!nl) nl = memchr(text + pos + budget, '\n', size - pos - (size_t)budget);
+    if (nl) stop = (size_t)((const char*)nl - text) + 1;
+  }
+  return stop;
 }
 
 struct ImportHeader {
@@ -157,10 +199,12 @@ struct ImpHostLine {
 
 // the 4 bytes of a deferred token, by the host importer's own parsers (which throw what the host importer throws)
 inline uint32_t resolve_deferred(const gdbimp::ImpDeferred& d, const char* text, const ImportTablesHost& H) {
-  std::string what = d.what == gdbimp::IMP_WHAT_QUAL ? "QUAL" : d.what == gdbimp::IMP_WHAT_GT ? "GT"
+  std::string what = d.what == gdbimp::IMP_WHAT_QUAL ? "QUAL" : d.what == gdbimp::IMP_WHAT_GT ? "GT" : d.what == gdbimp::IMP_WHAT_FILTER ? "FILTER"
                      : d.what >= gdbimp::IMP_WHAT_FMT_BASE ? H.fmt_names.at((size_t)(d.what - gdbimp::IMP_WHAT_FMT_BASE)) : H.info_names.at((size_t)d.what);
   union { float f; uint32_t u; int32_t i; } x;
-  if (d.kind == gdbimp::IMP_KIND_INT) {
+  if (d.kind == gdbimp::IMP_KIND_CSV_INT) x.i = (int32_t)import_csv_parse_int(text + d.tok_off, d.tok_len, what);      // truncated to the attribute's width
+  else if (d.kind == gdbimp::IMP_KIND_CSV_FLOAT) x.f = import_csv_parse_float(text + d.tok_off, d.tok_len, what);
+  else if (d.kind == gdbimp::IMP_KIND_INT) {
     int64_t v = import_parse_int(text + d.tok_off, d.tok_len, what);
     if (d.divide) v = gdbimp::imp_divide_among_samples(v, (int)d.divide, (int)d.sample_idx);
     x.i = (int32_t)v;
@@ -216,6 +260,21 @@ inline std::string describe_line_error(uint32_t bit, const ImportTablesHost& H, 
     default: break;
   }
   return "malformed record (" + where + ")";
+}
+
+// the same for a line of a CSV cell file (ImpCsvErr bits, core/gdb_import_csv.hpp)
+inline std::string describe_csv_error(uint32_t bit, const std::string& where) {
+  using namespace gdbimp;
+  switch (bit) {
+    case IMP_ERR_CSV_QUOTE: return "a '\"' in a CSV line: quoted tokens are not imported (" + where + ")";
+    case IMP_ERR_CSV_COORD: return "row, column or END of a CSV line cannot be parsed as a 64-bit integer (" + where + ")";
+    case IMP_ERR_CSV_COUNT: return "a count token of a CSV line is null, negative, not a number or runs past the line (" + where + ")";
+    case IMP_ERR_CSV_EXTRA: return "tokens left over after the last attribute of a CSV line (" + where + ")";
+    case IMP_ERR_CSV_OPEN: return "a CSV line ends before its last attribute (" + where + ")";
+    case IMP_ERR_COORD_RANGE: return "a column outside what the device importer's (column, row) sort key holds (" + where + ")";
+    default: break;
+  }
+  return "malformed CSV line (" + where + ")";
 }
 
 inline uint32_t first_import_error_bit(uint32_t bits) { for (uint32_t b = 1; b; b <<= 1) if (bits & b) return b; return 0; }

@@ -207,6 +207,20 @@ struct Cell { int64_t row, col; size_t off, len; };
 
 int64_t import_parse_int(const char* p, size_t n, const std::string& what) { return parse_int(Tok{p, n}, what); }
 double import_parse_double(const char* p, size_t n, const std::string& what) { return parse_double(Tok{p, n}, what); }
+int64_t import_csv_parse_int(const char* p, size_t n, const std::string& what) {
+  const std::string s(p, n);
+  char* end = nullptr;
+  const long long v = strtoll(s.c_str(), &end, 0);
+  if (end == s.c_str()) throw VCF2BinaryException("field " + what + ": cannot convert '" + s + "' to an integer");
+  return (int64_t)v;
+}
+float import_csv_parse_float(const char* p, size_t n, const std::string& what) {
+  const std::string s(p, n);
+  char* end = nullptr;
+  const float v = strtof(s.c_str(), &end);
+  if (end == s.c_str()) throw VCF2BinaryException("field " + what + ": cannot convert '" + s + "' to a float");
+  return v;
+}
 
 std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const ImportOptions& opt, ImportStats* stats) {
   if (!vid.is_initialized() || !vid.is_callset_mapping_initialized()) throw VCF2BinaryException("vid and callset mappings are needed");
@@ -254,6 +268,8 @@ std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const Import
   std::vector<uint8_t> body;
   for (const std::string& fn : files) {
     const std::string path = (!fn.empty() && fn[0] != '/' && !opt.file_root.empty()) ? opt.file_root + "/" + fn : fn;
+    if (vid.get_file_type(fn) != GDB_FILE_VCF)
+      throw VCF2BinaryException(path + " is a CSV cell file: CSV input needs the device importer (import_callsets_to_cells_device, vcf2tiledb --import-on-device); the host importer reads VCF text");
     const std::string text = read_text_maybe_gz(path);
     if (text.size() >= 5 && memcmp(text.data(), "BCF\2", 4) == 0 && (text[4] == 1 || text[4] == 2))      // the content decides, plain or compressed
       throw VCF2BinaryException(path + " is BCF2: BCF2 input needs the device importer (import_callsets_to_cells_device, vcf2tiledb --import-on-device); the host importer reads VCF text");

@@ -11,8 +11,9 @@
 //          [INFO attributes in vid order][FORMAT attributes in vid order]
 //          fixed-length attribute = num x element (missing: TileDB null), var-length = i32 num + num x element (missing: num 0)
 //
-// Not done (documented in DESIGN.md): htslib's record-level checks, CSV input, fields of more than 2 dimensions.  BCF2 files
-// and buffer streams are read by the device path only (host/import_bcf.hpp); import_callsets_to_cells refuses a BCF2 file by name.  2-dimensional (allele-specific) fields and intervals that reach across a partition begin ARE imported by
+// Not done (documented in DESIGN.md): htslib's record-level checks, fields of more than 2 dimensions.  BCF2 files, buffer streams
+// and CSV cell files (the "sorted_csv_files" / "unsorted_csv_files" of the callset mapping; core/gdb_import_csv.hpp) are read by the
+// device path only (host/import_bcf.hpp); import_callsets_to_cells refuses a BCF2 file and a CSV file by name.  2-dimensional (allele-specific) fields and intervals that reach across a partition begin ARE imported by
 // import_callsets_to_cells; the device path (import_callsets_to_cells_device, kernels/gdb_import.hip) refuses 2-dimensional
 // fields and flattened tuple elements by name and leaves those vids to the host importer.
 #pragma once
@@ -60,7 +61,8 @@ std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const Import
 // import_callsets_to_cells refuses; a BGZF member whose stream, ISIZE or CRC32 is wrong refuses the file.
 // BCF2 files (sniffed by content, plain or compressed) are imported too; compressed BCF2 is inflated on the host and is an error in
 // inflate_mode 2.  streams: a callset file whose "filename" equals a stream's name is read from that memory instead (VCF text or
-// BCF2, plain or gzip); a stream that no callset names is an error.
+// BCF2, plain or gzip); a stream that no callset names is an error.  A file or stream that the callset mapping lists as a CSV cell
+// file is read as one (one line = one cell; not replayed at a partition begin; compressed content is refused).
 struct ImportStream { std::string name; const void* data = nullptr; uint64_t nbytes = 0; };
 std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes,
                                                      ImportStats* stats = nullptr, int inflate_mode = 0,
@@ -70,5 +72,9 @@ std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const
 // them on the tokens it deferred
 int64_t import_parse_int(const char* p, size_t n, const std::string& what);
 double import_parse_double(const char* p, size_t n, const std::string& what);
+// the CSV reader's (reference include/vcf/vcf.h:238-313): strtoll(token, &end, 0) / strtof(token, &end) over a PREFIX of the token -
+// leading whitespace, a sign, 0x and 0 prefixes, trailing text ignored - and VCF2BinaryException when nothing can be parsed
+int64_t import_csv_parse_int(const char* p, size_t n, const std::string& what);
+float import_csv_parse_float(const char* p, size_t n, const std::string& what);
 
 }  // namespace genomicsdb_amd

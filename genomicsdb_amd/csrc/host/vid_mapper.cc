@@ -260,6 +260,14 @@ void VidMapper::parse_callsets_json(const mini_json::Value& doc) {
     if (d.HasMember("filename")) ci.m_filename = d["filename"].GetString();
     m_callsets.push_back(ci);
   }
+  const mini_json::Value& lists = doc.HasMember("callsets") ? doc : doc["callset_mapping"];
+  for (int sorted = 0; sorted < 2; ++sorted) {
+    const char* key = sorted ? "sorted_csv_files" : "unsorted_csv_files";
+    if (!lists.HasMember(key)) continue;
+    const mini_json::Value& l = lists[key];
+    if (!l.IsArray()) throw VidMapperException(std::string("\"") + key + "\" must be a list of file names");
+    for (size_t i = 0; i < l.Size(); ++i) m_csv_files[l[i].GetString()] = sorted ? GDB_FILE_SORTED_CSV : GDB_FILE_UNSORTED_CSV;
+  }
   m_is_callset_mapping_initialized = true;
 }
 

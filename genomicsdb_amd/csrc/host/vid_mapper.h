@@ -57,6 +57,10 @@ struct ContigInfo { std::string m_name; int64_t m_tiledb_column_offset = 0, m_le
 // one entry of the callset mapping (reference vid_mapper.cc:88-146 CallSetInfo: row, file, index of the sample in the file)
 struct CallSetInfo { std::string m_name; int64_t m_row_idx = -1, m_idx_in_file = 0; std::string m_filename; };
 
+// how a callset file is read: VCF text / BCF2 (told apart by content) or a CSV cell file, named in the callset mapping's
+// "sorted_csv_files" / "unsorted_csv_files" lists (reference vid_mapper.cc, FileBasedVidMapper::parse_callsets_json)
+enum GdbFileType { GDB_FILE_VCF = 0, GDB_FILE_SORTED_CSV = 1, GDB_FILE_UNSORTED_CSV = 2 };
+
 class VidMapper {
  public:
   void parse_vid_json(const mini_json::Value& doc);
@@ -74,6 +78,8 @@ class VidMapper {
   bool get_callset_name(int64_t row_idx, std::string& name) const;
   int64_t get_num_callsets() const { return (int64_t)m_row_idx_to_name.size(); }
   const std::vector<CallSetInfo>& get_callsets() const { return m_callsets; }   // mapping order
+  // by the callsets' "filename" string; a name in a CSV list that no callset uses is ignored
+  GdbFileType get_file_type(const std::string& filename) const { auto it = m_csv_files.find(filename); return it == m_csv_files.end() ? GDB_FILE_VCF : it->second; }
   // attribute order of the array schema (reference vid_mapper.cc:354-442): END, REF, ALT, [ID], QUAL, FILTER, INFO.., FORMAT..
   std::vector<std::string> schema_attribute_names() const;
  private:
@@ -84,6 +90,7 @@ class VidMapper {
   std::vector<std::pair<int64_t, int>> m_contig_begin_2_idx;
   std::vector<std::string> m_row_idx_to_name;
   std::vector<CallSetInfo> m_callsets;
+  std::unordered_map<std::string, GdbFileType> m_csv_files;
   bool m_is_initialized = false, m_is_callset_mapping_initialized = false;
 };
 

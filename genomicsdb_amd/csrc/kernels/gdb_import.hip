@@ -26,6 +26,12 @@
 // record boundaries and uploads the bytes and the record offsets; k_imp_bcf_index - one thread per record - takes the place of the
 // newline / tab index and leaves a table per record (core/gdb_import_bcf.hpp); measure, write and finish() are the kernels above,
 // instantiated over ImpBcfSrc instead of ImpTextSrc, one thread per (record, imported sample).
+//
+// CSV cell files (the callset mapping's "sorted_csv_files" / "unsorted_csv_files"; core/gdb_import_csv.hpp): the text path's newline
+// index, batch cuts, LDS staging, key sort and gather, instantiated over ImpCsvSrc.  A line is one slot and names its own row, which
+// is looked up in the ascending table of the file's rows; its slots carry no partition-begin tag, so k_imp_resolve leaves them alone
+// (and is not launched when no other source queued a batch).  Both passes walk the line's tokens: there is no per-line token index,
+// see profiles/device_import_csv.md.
 #include "gdb_import.h"
 
 #include <hip/hip_runtime.h>
@@ -40,6 +46,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <type_traits>
 
 #include "../common/gz_text.hpp"
 #include "../host/import_bcf.hpp"
@@ -63,7 +70,7 @@ constexpr int kBlock = 256;              // 4 wavefronts
 constexpr int kBytesPerThread = 16;      // one 16-byte load
 constexpr uint32_t kTile = kBlock * kBytesPerThread;
 constexpr uint32_t kTextPad = 64;        // bytes behind the text that the 16-byte loads may touch
-constexpr int kErrWords = 16;            // [0]: ImpErr bits, [1 + b]: smallest line that raised bit b
+constexpr int kErrWords = 20;            // [0]: ImpErr bits, [1 + b]: smallest line that raised bit b
 constexpr uint64_t kDroppedKey = ~(uint64_t)0;
 
 struct ImpBatch { const char* text; const uint32_t* nl_pos; const uint32_t* line_first_tab; const uint32_t* tab_pos; uint32_t n_lines; };
@@ -159,26 +166,49 @@ struct ImpSamples { const int32_t* file_idx; const int64_t* row; int32_t n; };  
 struct ImpSpan { unsigned long long* row_best; int32_t seq_bits; uint64_t line_seq_base; int64_t max_row; };   // row_best null: no partition begin
 
 // Where the slots of a batch come from: record lines of text (index: newlines and tabs) or BCF2 records (index: k_imp_bcf_index).
-// measure / write are the two passes of one (line or record, sample of the file); is_record: the line counts as a record.
-struct ImpTextSrc {
+// measure / write are the two passes of one slot; is_record: the line counts as a record.  A slot of text or BCF2 is one (line or
+// record, imported sample of the file) and its row is the sample's; a slot of a CSV cell file is one line, which names its own row.
+struct ImpPerSample {
+  __device__ __forceinline__ uint32_t per_line(const ImpSamples& S) const { return S.n > 0 ? (uint32_t)S.n : 1u; }
+  __device__ __forceinline__ int sample_of(const ImpSamples& S, uint32_t j) const { return S.n > 0 ? S.file_idx[j] : -1; }
+  __device__ __forceinline__ int64_t row_of(const ImpSamples& S, uint32_t j) const { return S.n > 0 ? S.row[j] : -1; }
+};
+struct ImpTextSrc : ImpPerSample {
   ImpBatch B;
   __device__ __forceinline__ ImpSlot measure(const ImpTables& T, uint32_t line, int sample, bool* is_record) const {
     const ImpLine L = imp_line_of(B, line);
     *is_record = L.end > L.begin && B.text[L.begin] != '#';
     return imp_measure(T, L, sample);
   }
-  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t line, int sample, int64_t row, const ImpSlot& s, ImpSink<true>& o) const {
-    return imp_write(T, imp_line_of(B, line), sample, row, s, o);
+  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t line, int sample, int64_t* row, const ImpSlot& s, ImpSink<true>& o) const {
+    return imp_write(T, imp_line_of(B, line), sample, *row, s, o);
   }
 };
-struct ImpBcfSrc {
+struct ImpBcfSrc : ImpPerSample {
   ImpBcfTables BT; const uint8_t* bytes; const ImpBcfRec* rec; const ImpBcfField* fld; uint32_t n_attr;
   __device__ __forceinline__ ImpSlot measure(const ImpTables& T, uint32_t r, int sample, bool* is_record) const {
     *is_record = true;
     return imp_bcf_measure(T, BT, bytes, rec[r], fld + (uint64_t)r * n_attr, sample);
   }
-  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t r, int sample, int64_t row, const ImpSlot& s, ImpSink<true>& o) const {
-    return imp_bcf_write(T, BT, bytes, rec[r], fld + (uint64_t)r * n_attr, sample, row, s, o);
+  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t r, int sample, int64_t* row, const ImpSlot& s, ImpSink<true>& o) const {
+    return imp_bcf_write(T, BT, bytes, rec[r], fld + (uint64_t)r * n_attr, sample, *row, s, o);
+  }
+};
+// a line of a CSV cell file (core/gdb_import_csv.hpp): the newline index of the text path finds it, both passes walk its tokens once
+// (no per-line token index: profiles/device_import_csv.md), rows: the rows of the file's callsets, ascending
+struct ImpCsvSrc {
+  ImpBatch B; ImpCsvRows rows;
+  __device__ __forceinline__ uint32_t per_line(const ImpSamples&) const { return 1u; }
+  __device__ __forceinline__ int sample_of(const ImpSamples&, uint32_t) const { return 0; }
+  __device__ __forceinline__ int64_t row_of(const ImpSamples&, uint32_t) const { return -1; }       // (the write pass reads it from the line)
+  __device__ __forceinline__ ImpSlot measure(const ImpTables& T, uint32_t line, int, bool* is_record) const {
+    const ImpLine L = imp_line_of(B, line);
+    *is_record = L.end > L.begin;
+    int64_t row;
+    return imp_csv_measure(T, rows, L, &row);
+  }
+  __device__ __forceinline__ uint32_t write(const ImpTables& T, uint32_t line, int, int64_t* row, const ImpSlot& s, ImpSink<true>& o) const {
+    return imp_csv_write(T, imp_line_of(B, line), s, o, row);
   }
 };
 
@@ -198,17 +228,17 @@ template <class Src>
 __global__ void __launch_bounds__(kBlock) k_imp_measure(ImpTables T, Src src, ImpSamples S, ImpSpan P, uint64_t n_slots, int64_t* col, int64_t* end,
                                                        uint64_t* size, uint8_t* kind, uint32_t* err, unsigned long long* counters) {
   const uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t per_line = S.n > 0 ? (uint32_t)S.n : 1u;
+  const uint32_t per_line = src.per_line(S);
   bool is_record = false, is_cell = false;
   if (slot < n_slots) {
     const uint32_t line = (uint32_t)(slot / per_line), j = (uint32_t)(slot % per_line);
-    const int sample = S.n > 0 ? S.file_idx[j] : -1;
+    const int sample = src.sample_of(S, j);
     bool record_line = false;
     const ImpSlot s = src.measure(T, line, sample, &record_line);
     is_record = j == 0u && record_line;
     if (s.err) imp_raise(err, s.err, line);
     else if (P.row_best && sample >= 0 && record_line && s.col <= T.column_end && s.col <= T.column_begin) {
-      const int64_t row = S.row[j];
+      const int64_t row = src.row_of(S, j);
       if (row >= 0 && row <= P.max_row)
         atomicMax(&P.row_best[row], ((unsigned long long)s.col << P.seq_bits) | (unsigned long long)(P.line_seq_base + line + 1u));
     }
@@ -241,22 +271,24 @@ __global__ void __launch_bounds__(kBlock) k_imp_write(ImpTables T, Src from, Imp
   const bool staged = STAGE && block_end <= cells_bytes && block_end - block_base + pad <= (uint64_t)kStageBytes;
   const uint64_t slot = first + threadIdx.x;
   if (slot < n_slots) {
-    const uint32_t per_line = S.n > 0 ? (uint32_t)S.n : 1u;
+    const uint32_t per_line = from.per_line(S);
     const uint32_t line = (uint32_t)(slot / per_line), j = (uint32_t)(slot % per_line);
+    const int sample = from.sample_of(S, j);
     uint64_t key = kDroppedKey, tag = 0, src = 0;
     uint32_t sz = 0;
     const uint8_t k = kind[slot];
-    if (k != IMP_SLOT_NONE && S.n > 0) {
+    if (k != IMP_SLOT_NONE && sample >= 0) {
       ImpSlot s; s.col = col[slot]; s.end = end[slot]; s.size = size[slot]; s.kind = k; s.err = 0;
       const uint64_t at = off[slot];
       // (always true, by the scan: nothing is stored outside the batch's cells, nor outside the block's range of them)
       if (at >= block_base && at + s.size <= block_end && at + s.size <= cells_bytes && s.size < ((uint64_t)1 << 32)) {
-        const int64_t row = S.row[j];
+        int64_t row = from.row_of(S, j);
         ImpSink<true> o;
         o.out = staged ? s_stage + (at - block_base) + pad : cells + at;
         o.base = at; o.def = def; o.ndef = ndef; o.def_cap = def_cap; o.line = line;
-        const uint32_t e = from.write(T, line, S.file_idx[j], row, s, o);
+        const uint32_t e = from.write(T, line, sample, &row, s, o);
         if (e) imp_raise(err, e, line);
+        if (row < 0 || row > P.max_row) row = 0;      // (never: a kept slot's row is a row of the mapping)
         key = imp_sort_key(T, s.col, row);
         src = (uint64_t)(uintptr_t)(cells + at);
         sz = (uint32_t)s.size;
@@ -345,6 +377,7 @@ struct DeviceImporter::Impl {
   DBuf<unsigned long long> d_row_best, d_counters;
   DBuf<uint32_t> d_err, d_ndef;
   bool spanning = false; int seq_bits = 64; uint64_t line_seq = 0;
+  bool spanning_slots = false;       // a batch whose slots take part in the partition-begin rule was queued (never a CSV batch)
   bool stage_in_lds = true;          // the A/B of profiles/device_import.md: -7.5 % on the write kernel; GDBAMD_IMPORT_STAGE_LDS=0|1 overrides
   // per batch, reused
   DBuf<char> d_text, d_tmp;
@@ -387,11 +420,13 @@ struct DeviceImporter::Impl {
     batches.clear();
   }
   // text: host text to upload, or null when the batch is already in d_text; -> lines of the batch
-  uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp);
+  // n_csv_rows >= 0: the lines are those of a CSV cell file, and d_samp_row holds that many rows of the file, ascending
+  uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp, int n_csv_rows = -1);
   int upload_samples(const ImportHeader& hdr);                              // -> imported samples of the file
   void append_text(const ImportFile& file, const std::string& text);        // inflated text of a whole file, on the host
   void append_bgzf(const ImportFile& file, const std::string& raw, const std::vector<BgzfMember>& mem);
   void append_bcf(const ImportFile& file, const char* data, size_t n);      // a whole BCF2 stream, inflated
+  void append_csv(const ImportFile& file, const char* data, size_t n);      // a whole CSV cell file
   const ImportFile& file_named(const std::string& filename) const;
   // measure, layout and write of the n_lines x max(n_imp, 1) slots of a batch whose index pass is queued (ev[0], ev[1] recorded).
   // host_text: the batch's text for the deferred tokens; describe(bit, line) / where(line): the words of an error
@@ -417,6 +452,7 @@ DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOpt
     if (const char* e = getenv("GDBAMD_INFLATE_KERNEL")) m_->inflater.set_kernel(std::string(e) == "thread" ? BgzfDeviceInflater::kThreadPerMember : BgzfDeviceInflater::kWavePerMember);
     m_->H = build_import_tables(vid);                 // the refusals: before the device is touched
     m_->files = import_files(vid, opt);
+    refuse_for_csv(vid, m_->H, m_->files);
     Impl& M = *m_;
     if (opt.column_begin > 0) {
       int col_bits = 0;
@@ -502,6 +538,20 @@ void DeviceImporter::append_file(const std::string& filename) {
   IMP_HIP_CHECK(hipSetDevice(M.device));
   const ImportFile* file = &M.file_named(filename);
   const double t0 = now_s();
+  if (file->type != GDB_FILE_VCF) {       // the callset mapping decides; read as it is
+    std::ifstream in(file->path, std::ios::binary);
+    if (!in) throw VCF2BinaryException("cannot open " + file->path);
+    in.seekg(0, std::ios::end);
+    const std::streamoff size = in.tellg();
+    in.seekg(0, std::ios::beg);
+    std::string data(size > 0 ? (size_t)size : 0, '\0');
+    if (!data.empty() && !in.read(&data[0], (std::streamsize)data.size())) throw VCF2BinaryException("cannot read " + file->path);
+    M.st.s_read += now_s() - t0;
+    M.st.compressed_bytes += data.size();
+    ++M.st.num_files;
+    M.append_csv(*file, data.data(), data.size());
+    return;
+  }
   if (file_is_bcf2(file->path)) {       // the content decides, plain or compressed; BCF2 records cross BGZF members, so the host inflates
     if (M.inflate_mode == kInflateDevice)
       throw VCF2BinaryException(file->path + " is BCF2: BCF2 input is inflated on the host in this build, and inflating on the device was required");
@@ -578,16 +628,29 @@ void DeviceImporter::Impl::append_text(const ImportFile& file_, const std::strin
   size_t pos = hdr.record_begin;
   int64_t lines_before = hdr.lines_before;
   while (pos < text.size()) {
-    size_t stop = text.size();
-    if (stop - pos > M.budget) {
-      const void* nl = memrchr(text.data() + pos, '\n', (size_t)M.budget);
-      if (!nl) nl = memchr(text.data() + pos + M.budget, '\n', text.size() - pos - (size_t)M.budget);
-      if (nl) stop = (size_t)((const char*)nl - text.data()) + 1;
-    }
+    const size_t stop = import_text_cut(text.data(), text.size(), pos, M.budget);
     const size_t n = stop - pos;
     if (n >= ((size_t)1 << 31)) throw VCF2BinaryException("a record line of 2 GiB or more in " + file->path);
     const bool add_newline = text[stop - 1] != '\n';
     lines_before += M.batch(*file, hdr, text.data() + pos, n, add_newline, lines_before, n_imp);
+    pos = stop;
+  }
+}
+
+void DeviceImporter::Impl::append_csv(const ImportFile& file, const char* data, size_t size) {
+  refuse_compressed_csv(data, size, file.path);
+  const std::vector<int64_t> rows = csv_rows_of(file);
+  d_samp_row.ensure(std::max<size_t>(rows.size(), 1));
+  IMP_HIP_CHECK(hipMemcpyAsync(d_samp_row.p, rows.data(), rows.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  const ImportHeader none;
+  size_t pos = 0;
+  int64_t lines_before = 0;
+  while (pos < size) {
+    const size_t stop = import_text_cut(data, size, pos, budget);
+    const size_t n = stop - pos;
+    if (n >= ((size_t)1 << 31)) throw VCF2BinaryException("a line of 2 GiB or more in " + file.path);
+    lines_before += batch(file, none, data + pos, n, data[stop - 1] != '\n', lines_before, 1, (int)rows.size());
     pos = stop;
   }
 }
@@ -709,7 +772,8 @@ void DeviceImporter::Impl::append_bgzf(const ImportFile& file, const std::string
   }
 }
 
-uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n_text, bool add_newline, int64_t lines_before, int n_imp) {
+uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n_text, bool add_newline, int64_t lines_before, int n_imp,
+                                     int n_csv_rows) {
   const uint32_t n = (uint32_t)(n_text + (add_newline ? 1 : 0));
   ++st.num_batches;
   st.text_bytes += n_text;
@@ -759,6 +823,11 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   BatchWords words;
   words.host_text = host_text; words.n_text = n_text;
   words.where = [&](uint32_t line) { return file.path + " line " + std::to_string(lines_before + (int64_t)line + 1); };
+  if (n_csv_rows >= 0) {
+    words.describe = [&](uint32_t bit, uint32_t line) { return describe_csv_error(bit, words.where(line)); };
+    cells_of_batch(ImpCsvSrc{ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}, ImpCsvRows{d_samp_row.p, n_csv_rows}}, T, n_lines, n_imp, words);
+    return n_lines;
+  }
   words.describe = [&](uint32_t bit, uint32_t line) {
     uint32_t lb = 0, le = 0;
     if (line) { IMP_HIP_CHECK(hipMemcpy(&lb, d_nl.p + (line - 1), sizeof(uint32_t), hipMemcpyDeviceToHost)); ++lb; }
@@ -766,7 +835,7 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
     le = std::min<uint32_t>(le, (uint32_t)n_text);
     return describe_line_error(bit, H, opt, hdr, host_text(), lb, le, words.where(line));
   };
-  cells_of_batch(ImpTextSrc{ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}}, T, n_lines, n_imp, words);
+  cells_of_batch(ImpTextSrc{{}, ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}}, T, n_lines, n_imp, words);
   return n_lines;
 }
 
@@ -778,7 +847,9 @@ template <class Src> void DeviceImporter::Impl::cells_of_batch(const Src& src, c
   if (total_slots + n_slots >= ((uint64_t)1 << 32)) throw VCF2BinaryException("more than 2^32 (record line, sample) pairs in one device import: split the callset mapping");
   d_col.ensure(n_slots); d_end.ensure(n_slots); d_size.ensure(n_slots + 1); d_off.ensure(n_slots + 1); d_kind.ensure(n_slots);
   const ImpSamples S{d_samp_idx.p, d_samp_row.p, n_imp};
-  const ImpSpan P{spanning ? d_row_best.p : nullptr, seq_bits, line_seq, H.max_row};
+  const bool by_sample = !std::is_same<Src, ImpCsvSrc>::value;     // a CSV line is never replayed at the partition begin: no row_best, no tags
+  const ImpSpan P{spanning && by_sample ? d_row_best.p : nullptr, seq_bits, line_seq, H.max_row};
+  spanning_slots = spanning_slots || (spanning && by_sample);
   IMP_HIP_CHECK(hipMemsetAsync(d_err.p, 0, sizeof(uint32_t), stream));
   IMP_HIP_CHECK(hipMemsetAsync(d_err.p + 1, 0xFF, (kErrWords - 1) * sizeof(uint32_t), stream));
   IMP_HIP_CHECK(hipMemsetAsync(d_counters.p, 0, 2 * sizeof(unsigned long long), stream));
@@ -912,7 +983,7 @@ void DeviceImporter::Impl::append_bcf(const ImportFile& file, const char* data, 
     words.describe = [&](uint32_t bit, uint32_t r) {
       return describe_bcf_error(bit, H, opt, hdr, (const uint8_t*)data + base, rel[r], rel[r + 1u], words.where(r));
     };
-    cells_of_batch(ImpBcfSrc{BT, (const uint8_t*)d_text.p, d_rec.p, d_fld.p, n_attr}, T, n_rec, n_imp, words);
+    cells_of_batch(ImpBcfSrc{{}, BT, (const uint8_t*)d_text.p, d_rec.p, d_fld.p, n_attr}, T, n_rec, n_imp, words);
     first = last;
   }
 }
@@ -930,6 +1001,13 @@ void DeviceImporter::append_buffer(const std::string& name, const void* ptr, uin
   if (!ptr && nbytes) throw VCF2BinaryException("stream " + name + ": null data");
   const char* data = (const char*)ptr;
   const double t0 = now_s();
+  if (file.type != GDB_FILE_VCF) {
+    M.st.s_read += now_s() - t0;
+    M.st.compressed_bytes += nbytes;
+    ++M.st.num_files;
+    M.append_csv(file, data, (size_t)nbytes);
+    return;
+  }
   std::string inflated;
   const bool gz = is_gzip(data, (size_t)nbytes);
   if (gz) {
@@ -984,7 +1062,7 @@ void DeviceImporter::finish(std::vector<uint8_t>& cells) {
     at += b.n_slots;
   }
   IMP_HIP_CHECK(hipMemsetAsync(M.d_counters.p, 0, 4 * sizeof(unsigned long long), st));
-  if (M.spanning)
+  if (M.spanning_slots)
     hipLaunchKernelGGL(k_imp_resolve, dim3(grid_for(N)), dim3(kBlock), 0, st, key.p, (const uint64_t*)tag.p, N, (const unsigned long long*)M.d_row_best.p, M.H.key_row_bits,
                        M.H.max_row, M.d_counters.p);
   hipLaunchKernelGGL(k_imp_iota, dim3(grid_for(N)), dim3(kBlock), 0, st, idx.p, N);
