@@ -145,6 +145,12 @@ def build_hostsim_inflate():
     return os.path.join(ROOT, "tests", "hostsim_inflate", "libhostsim_inflate.so")
 
 
+def build_hostsim_dispatch():
+    """CPU harness around the choice of an interval's sizing and page kernels (kernels/gdb_assembly_choice.hpp; tests only)"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_dispatch")])
+    return os.path.join(ROOT, "tests", "hostsim_dispatch", "libhostsim_dispatch.so")
+
+
 if __name__ == "__main__":
     print(build_native(verbose=True))
     print(build_oracle())

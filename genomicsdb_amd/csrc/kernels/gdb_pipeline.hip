@@ -31,6 +31,7 @@
 #include "../core/gdb_variants.hpp"
 #include "gdb_pipeline.h"
 #include "gdb_bgzf.h"
+#include "gdb_assembly_choice.hpp"
 
 namespace genomicsdb_amd {
 
@@ -103,63 +104,19 @@ template <class T> struct DevBuf {   // grow-only device allocation
 
 inline bool debug_sync() { static int v = -1; if (v < 0) { const char* e = getenv("GDBAMD_DEBUG_SYNC"); v = (e && *e && *e != '0') ? 1 : 0; } return v == 1; }
 #define STAGE(name) do { if (debug_sync()) { HIP_CHECK(hipStreamSynchronize(st)); fprintf(stderr, "[gdbamd] stage %s\n", name); fflush(stderr); } } while (0)
-// Records one wavefront takes in a row.  Measured on c2 (200 kb windows): the sizing pass, which starts every run with a
-// binary search per sample, is fastest at 64; the page pass (no per-run set-up beyond one 64-lane scalar fetch) at 32 -
-// more, shorter runs balance better across the 256 CUs than longer ones amortise.  GDBAMD_RUN / GDBAMD_RUN_W override.
-inline int size3_rounds();
-inline int size_run_length() { const char* e = getenv("GDBAMD_RUN"); return e && *e ? std::max(1, atoi(e)) : size3_rounds() ? 128 : 64; }   // (the piece-wise kernel: 128 measured 0.3 ms faster than 64, 256 slower)
-inline int write_run_length() { const char* e = getenv("GDBAMD_RUN_W"); return e && *e ? std::max(1, atoi(e)) : 32; }
 // record types that get text-table slots (GDBAMD_MAX_TYPES < 64 forces the direct path in tests)
 inline int max_tabled_types() {
   const char* e = getenv("GDBAMD_MAX_TYPES");   // read per interval: tests flip it in-process
   return e && *e ? std::max(0, std::min(64, atoi(e))) : 64;
 }
-// HBM the resolved (record, sample) matrix of a whole interval may take (8 bytes x records x samples rounded up to 64);
-// wider intervals resolve page by page.  GDBAMD_RESOLVED_MB overrides (tests use 0 to force the per-page path).
-inline uint64_t resolved_budget_bytes() {
-  const char* e = getenv("GDBAMD_RESOLVED_MB");
-  return e && *e ? (uint64_t)atoll(e) << 20 : (uint64_t)32 << 30;
-}
-// records per (run, chunk) of the change-list page assembly (<= 64); GDBAMD_EVENTS=1 selects it instead of the dense matrix
-inline int event_run_length() { const char* e = getenv("GDBAMD_EV_RUN"); return e && *e ? std::max(1, std::min(64, atoi(e))) : 32; }
-// (off by default: measured slower than the dense matrix, with scalar loads of the changes and with vector loads + v_readlane)
-inline bool events_enabled() { const char* e = getenv("GDBAMD_EVENTS"); return e && *e && *e != '0'; }
-// How an interval's sample columns are sized and assembled (GDBAMD_ASM_PATH, read per interval; measured in DESIGN.md section 5):
-//   0 (default)  the sizing pass of rounds 1-3 (k_assemble_size: every (record, sample) pair walked, sizes and matrix in one pass), pages by k_assemble_write
-//   1            text only: sizes from pieces (k_size2), no matrix at all, the page pass walks the pieces itself (k_write2)
-//   2            sizes from pieces (k_size2), the matrix from a piece walker per lane (k_fill2), pages by k_assemble_write / the BCF kernels
-//   3            text only: sizes from pieces (k_size2), piece lists (k_plist), pages by k_write3 (no matrix, no walking in the page pass)
-inline int asm_path_wanted() { const char* e = getenv("GDBAMD_ASM_PATH"); return e && *e ? std::max(0, std::min(3, atoi(e))) : 0; }
-// sizing pass: 3 = k_assemble_size3 in rounds of 8 records (default), 16 = rounds of 16, 0 = k_assemble_size
-inline int size3_rounds() { const char* e = getenv("GDBAMD_SIZE3"); const int v = e && *e ? atoi(e) : 8; return v == 0 ? 0 : v >= 16 ? 16 : 8; }
-inline bool res_chunk_major() { static const bool v = []() { const char* e = getenv("GDBAMD_RES_LAYOUT"); return e && *e == '1'; }(); return v; }   // (measured: no difference; record-major stays)
-// compact resolved matrix (ResMatrix): 1 (default) whenever the interval allows it, 0 never (A/B runs); the check mode of the sizing
-// kernels compares the wide layout word for word, so it keeps that one
-inline bool size3_check();
-inline bool res_compact_wanted();
-inline bool size3_check() { const char* e = getenv("GDBAMD_SIZE3_CHECK"); return e && *e && *e != '0'; }
-inline bool res_compact_wanted() { if (size3_check()) return false; const char* e = getenv("GDBAMD_RES_COMPACT"); return !(e && *e == '0'); }
-inline int fill_run_length() { const char* e = getenv("GDBAMD_RUN_F"); return e && *e ? std::max(1, atoi(e)) : 128; }
-inline int write2_run_length() { const char* e = getenv("GDBAMD_RUN_W2"); return e && *e ? std::max(1, atoi(e)) : 64; }
-// wavefronts (= neighbouring 64-sample chunks) per workgroup of the page assembly: 4 measured best on the store-only model
-inline int write_waves_per_group() { const char* e = getenv("GDBAMD_WRITE_WAVES"); return e && *e ? atoi(e) : 1; }
 inline bool slot_regroup() { static const bool v = []() { const char* e = getenv("GDBAMD_SLOT_REGROUP"); return !(e && *e == '0'); }(); return v; }
-// the page kernel on a high-priority stream: GDBAMD_PAGE_PRIORITY=0 / 1 overrides what the engine asked for (set_page_priority)
-inline int page_priority_env() { const char* e = getenv("GDBAMD_PAGE_PRIORITY"); return e && (*e == '0' || *e == '1') ? *e - '0' : -1; }
-inline bool coop_unroll_wanted() { const char* e = getenv("GDBAMD_COOP_UNROLL"); return !(e && *e == '0'); }   // (A/B: 0 keeps the word-by-word copy of long entries)
-inline bool xcd_aware_numbering() { const char* e = getenv("GDBAMD_XCD_AWARE"); return !(e && *e == '0'); }
-// LDS image of one (record, 64-sample chunk) of the page kernel.  GDBAMD_WRITE_IMAGE_KB = 4 / 6 / 8 forces one; otherwise by the
-// interval's average chunk: 4 KiB while a chunk (c2: 2.8 KB) and its alignment slack fit - more resident wavefronts per CU, 0.4-0.6 ms
-// of a 12 ms launch, three A/B rounds inside one call (profiles/r5_ab_image.txt) - and 8 KiB for wider entries (c3's width: ~6 KB
-// per chunk would take two passes through a 4 KiB image)
-inline int write_image_kb(uint64_t avg_chunk_bytes = 0) {
-  const char* e = getenv("GDBAMD_WRITE_IMAGE_KB");
-  if (e && *e) return atoi(e);
-  return avg_chunk_bytes && avg_chunk_bytes <= 3400 ? 4 : 8;
-}
-inline int order_block_log2() {
-  const char* e = getenv("GDBAMD_ORDER_BLOCK_LOG2");
-  return e && *e ? std::max(0, std::min(30, atoi(e))) : 12;
+// the knobs that select sizing and page kernels (gdb_assembly_choice.hpp), read from the environment: once per interval, GDBAMD_RES_LAYOUT once per process
+inline AssemblyKnobs interval_knobs() {
+  const KnobLookup env = [](const char* name) -> const char* { return getenv(name); };
+  static const bool chunk_major = res_layout_chunk_major(env);
+  AssemblyKnobs k = read_assembly_knobs(env);
+  k.res_chunk_major = chunk_major;   // (GDBAMD_RES_LAYOUT as the process started with it)
+  return k;
 }
 inline unsigned blocks_for(int64_t n, int b = kBlock) { return (unsigned)std::max<int64_t>(1, (n + b - 1) / b); }
 inline int bits_for(uint64_t max_value) { int b = 1; while (b < 64 && (max_value >> b)) ++b; return std::min(64, b + 1); }
@@ -1508,10 +1465,8 @@ __device__ __forceinline__ uint4 load_chunk(const char* __restrict__ src, uint32
 // matrix; k_assemble_write streams that matrix (coalesced, prefetched one record ahead), keeps the current text of each
 // sample in registers, and reads the pool only when a sample's slot changes.  The per-record scalars (index, start, type,
 // destination) are fetched 64 records at a time, one per lane, and broadcast with v_readlane.
-constexpr int kAsmRows = 64;         // samples per (record, chunk): one wavefront
-constexpr int kWaveLds = 8 * 1024;   // LDS image of one (record, chunk)
+// (kAsmRows, kWaveLds and kCooperativeEntry: gdb_assembly_choice.hpp, the host's choice of the kernels reads them too)
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
-constexpr int kCooperativeEntry = 512;   // entry texts longer than this are copied pool -> page by the whole wavefront, not through the LDS image
 
 __device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, l);
@@ -3878,11 +3833,13 @@ struct DevicePipeline::Impl {
     std::vector<uint64_t> rec_off;
     IntervalStats stats;
     SiteCtx sx; EntryCtx ex; RowIndex ri; SiteOut so; RecordTable rec; AsmCtx ac; PieceCtx pc2;
-    bool resolved_whole = false, piece_path = false, res_compact = false; int asm_path = 0, NT = 0; int64_t P_rows = 0;
-    bool bcf = false; int bcf_F = 0; BcfLayout lay{nullptr, nullptr, nullptr, nullptr};
-    bool events = false; int evrun = 0; EventBuf eb{nullptr, nullptr, nullptr, 0};
-    int size_kernel = 0;          // the S digit of IntervalStats::page_kernel: the sizing kernel prepare_interval launched
+    AssemblyKnobs knobs{};        // the knobs as prepare_interval found them, and what choose_sizing made of them: begin_page goes by these
+    AssemblySizing sz{};
+    int NT = 0, bcf_F = 0; BcfLayout lay{nullptr, nullptr, nullptr, nullptr};
+    EventBuf eb{nullptr, nullptr, nullptr, 0};
   } iv;
+  // the resolved (record, sample) matrix in the layout the interval's sizing chose
+  ResMatrix res_view() const { return iv.sz.res_compact ? ResMatrix{nullptr, res_off.p, res_len8.p} : ResMatrix{resolved.p, nullptr, nullptr}; }
 
   void* temp_storage(size_t bytes) { temp.ensure(bytes + 256); return temp.p; }
   template <class K, class V> void sort_pairs(const K* kin, K* kout, const V* vin, V* vout, size_t n, int end_bit) {
@@ -3941,12 +3898,11 @@ struct DevicePipeline::Impl {
   }
   // records [k0, k0+n) in (type, position) order -> order[]
   int64_t order_k0 = -1, order_n = -1;   // what `order` currently holds
-  void order_by_type(int64_t k0, int64_t n) {
+  void order_by_type(int64_t k0, int64_t n, int block_log2) {   // block_log2: AssemblyKnobs::order_block_log2 of the interval
     if (k0 == order_k0 && n == order_n) return;   // a page that is the whole interval reuses the sizing pass's order
     order_k0 = k0; order_n = n;
     // Types are grouped inside blocks of consecutive records, not over the whole range: a wavefront still walks ~100
     // same-type records, but the page stores and matrix reads in flight stay within a few tens of MB (TLB reach, DRAM pages).
-    const int block_log2 = order_block_log2();
     iota.ensure(n); order.ensure(n); order_keys.ensure(n); order_keys_sorted.ensure(n);
     hipLaunchKernelGGL(k_order_keys, dim3(blocks_for(n)), dim3(kBlock), 0, stream, (const uint8_t*)rtype.p, (int32_t)k0, n, block_log2, order_keys.p, iota.p);
     sort_pairs(order_keys.p, order_keys_sorted.p, iota.p, order.p, (size_t)n, std::min(32, 8 + bits_for((uint64_t)(n >> block_log2))));
@@ -5450,23 +5406,15 @@ std::string DevicePipeline::variants_text(int64_t qb, int64_t qe, bool with_inte
 }
 uint64_t DevicePipeline::variants_text_bytes() const { return m_->variants_bytes; }
 
-// the sizing / resolution pass of `n` records in `order` (piece-wise kernel by default; GDBAMD_SIZE3=0: the record-by-record one).
-// size_slots: elements of chunk_size (the check mode compares them all).  Returns the kernel it launched as the S digit of
-// IntervalStats::page_kernel; page_kernel_code() puts the digits together at the launch sites.
-enum { kSizeKernelPlain = 0, kSizeKernel3x8 = 1, kSizeKernel3x16 = 2, kSizeKernelPieces = 3, kSizeKernelEvents = 4 };
-enum { kPageKernelWrite = 1, kPageKernelWrite2 = 2, kPageKernelWrite3 = 3, kPageKernelEvents = 4, kPageKernelBcf = 5 };
-constexpr int page_kernel_code(int size_kernel, int page_kernel, int waves, int coop_u, int lds_bytes) {
-  return size_kernel * 100000 + page_kernel * 10000 + waves * 1000 + coop_u * 100 + lds_bytes / 1024;
-}
-static int launch_assemble_size(DevicePipeline::Impl& S, hipStream_t st, dim3 grid, const AsmCtx& ac, const int32_t* order, int64_t n, int32_t N, int nchunks, int run,
+// the sizing / resolution pass of `n` records in `order` by the kernel choose_sizing / choose_page named (kSizeKernelPlain, 3x8 or 3x16).
+// size_slots: elements of chunk_size (the check mode, GDBAMD_SIZE3_CHECK, compares them all).
+static void launch_assemble_size(DevicePipeline::Impl& S, hipStream_t st, int kernel, dim3 grid, const AsmCtx& ac, const int32_t* order, int64_t n, int32_t N, int nchunks, int run,
                                  uint64_t* chunk_size, size_t size_slots, ResMatrix resolved, int64_t resolved_base, int64_t res_rows) {
-  const int rounds = size3_rounds();
-  if (rounds == 0 || run > 64 * 1024) { hipLaunchKernelGGL(k_assemble_size, grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows); return kSizeKernelPlain; }
-  if (rounds >= 16) hipLaunchKernelGGL((k_assemble_size3<16>), grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows);
+  if (kernel == kSizeKernelPlain) { hipLaunchKernelGGL(k_assemble_size, grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows); return; }
+  if (kernel == kSizeKernel3x16) hipLaunchKernelGGL((k_assemble_size3<16>), grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows);
   else hipLaunchKernelGGL((k_assemble_size3<8>), grid, dim3(kAsmRows), 0, st, ac, order, n, N, nchunks, run, chunk_size, resolved, resolved_base, res_rows);
-  const int launched = rounds >= 16 ? kSizeKernel3x16 : kSizeKernel3x8;
-  if (!size3_check()) return launched;
-  const size_t nres = resolved.wide ? (size_t)n * (size_t)nchunks * kAsmRows : 0;     // (the check runs with the wide layout: res_compact_wanted())
+  if (!S.iv.knobs.size3_check) return;
+  const size_t nres = resolved.wide ? (size_t)n * (size_t)nchunks * kAsmRows : 0;     // (the check runs with the wide layout: AssemblyKnobs::res_compact)
   S.chk_count.ensure(1);
   HIP_CHECK(hipMemsetAsync(S.chk_count.p, 0, sizeof(unsigned long long), st));
   if (nres) S.chk_resolved.ensure(nres);
@@ -5478,12 +5426,12 @@ static int launch_assemble_size(DevicePipeline::Impl& S, hipStream_t st, dim3 gr
   if (chunk_size) hipLaunchKernelGGL(k_compare_words, dim3(blocks_for((int64_t)size_slots * 2)), dim3(kBlock), 0, st, (const uint32_t*)chunk_size, (const uint32_t*)S.chk_sizes.p, (int64_t)size_slots * 2, S.chk_count.p);
   const unsigned long long bad = S.read_back(S.chk_count.p);
   if (bad) throw GenomicsDBDeviceException("GDBAMD_SIZE3_CHECK: the piece-wise sizing pass differs from the record-by-record one in " + std::to_string(bad) + " words");
-  return launched;
 }
 
 void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   Impl& S = *m_;
   S.iv = Impl::IntervalState();
+  S.iv.knobs = interval_knobs();
   S.order_k0 = S.order_n = -1;
   S.order_iv_valid = false;
   HIP_CHECK(hipSetDevice(S.device));
@@ -5877,13 +5825,12 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
 #undef GDB_SLOT_KERNELS
   S.long_texts_seen = long_texts * 16 > NS;    // the wide strip of pass 0 pays when a sixteenth of the texts is long
   S.pool_ovf_need = std::max<uint64_t>(S.pool_ovf_need, shard_need);   // (units per shard)
-  int asm_path = events_enabled() ? 0 : (pl.bcf_mode && (asm_path_wanted() & 1)) ? 2 : asm_path_wanted();
-  if (asm_path == 3 && UR > 0) asm_path = 0;      // (records of untabled types have a slot per (record, sample): the piece lists do not carry them)
-  const bool piece_path = asm_path == 1 || asm_path == 3;   // matrix-free page assembly
+  const AssemblySizing sz = S.iv.sz = choose_sizing(S.iv.knobs, IntervalFacts{pl.bcf_mode != 0, P, N, UR > 0, any_over255});
+  const int asm_path = sz.asm_path;
   hipLaunchKernelGGL(k_slot_desc, dim3(blocks_for((int64_t)NS)), dim3(kBlock), 0, st, S.slot_len.p, S.slot_off.p, (int64_t)NS, asm_path == 1 ? (uint2*)nullptr : S.slot_desc.p,
                      pl.bcf_mode ? (char*)nullptr : S.pool.p, stt.inline_max);
   stats.num_record_types = ntypes;
-  stats.resolved_entry_bytes = (asm_path == 1 || asm_path == 3 || events_enabled()) ? 0 : ((asm_path == 0 && !any_over255 && res_compact_wanted()) ? 5 : 8);
+  stats.resolved_entry_bytes = sz.resolved_entry_bytes;
   stats.num_text_slots = (int64_t)NS;
   stats.text_pool_bytes = (int64_t)(NS * kSlotStride + pool_units * 16);
   STAGE("k_walk_window");
@@ -5899,43 +5846,33 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   PieceCtx pc2{S.row_ptr.p, S.rm_begin.p, S.walk.p, S.rstart.p, S.rtype.p, S.ubase.p, S.type_occ.p, S.slot_len.p, S.prefix_len.p, S.jhint.p,
                (uint32_t)kMaxTypes, (uint32_t)(kMaxTypes + SL), (uint32_t)(kMaxTypes + SL + (uint64_t)T), S.walk_epoch, N, P};
   // ---- S8b sample-column sizes + offsets ---------------------------------------------------------------------------
-  const int run = size_run_length();
-  const unsigned run_blocks = (unsigned)((P + run - 1) / run);
+  const int run = sz.run, frun = sz.frun, evrun = sz.evrun;
+  const dim3 size_grid((unsigned)((P + run - 1) / run) * (unsigned)nchunks);
   STAGE("k_assemble_size");
-  if (!piece_path) S.order_by_type(0, P);
-  const uint64_t resolved_bytes = (uint64_t)P * nchunks * kAsmRows * sizeof(uint2);
-  bool use_events = false;
-  EventBuf ebuf{nullptr, nullptr, nullptr, 0};
-  const bool resolved_whole = !piece_path && (pl.bcf_mode || (resolved_bytes <= resolved_budget_bytes() && !(events_enabled() && ((1 << order_block_log2()) % event_run_length()) == 0)));
-  // compact layout: the default kernels (text and BCF2), no entry longer than a byte can say
-  const bool res_compact = asm_path == 0 && !events_enabled() && !any_over255 && res_compact_wanted() && (!pl.bcf_mode || resolved_whole);
-  if (resolved_whole) {
-    if (res_compact) { S.res_off.ensure((size_t)P * nchunks * kAsmRows); S.res_len8.ensure((size_t)P * nchunks * kAsmRows); }
+  if (!sz.piece_path) S.order_by_type(0, P, S.iv.knobs.order_block_log2);
+  if (sz.resolved_whole) {
+    if (sz.res_compact) { S.res_off.ensure((size_t)P * nchunks * kAsmRows); S.res_len8.ensure((size_t)P * nchunks * kAsmRows); }
     else S.resolved.ensure((size_t)P * nchunks * kAsmRows);
   }
-  auto res_view = [&S, res_compact]() { return res_compact ? ResMatrix{nullptr, S.res_off.p, S.res_len8.p} : ResMatrix{S.resolved.p, nullptr, nullptr}; };
   S.max_record.ensure(1);
   HIP_CHECK(hipMemsetAsync(S.max_record.p, 0, sizeof(unsigned long long), st));
   BcfLayout lay{nullptr, nullptr, nullptr, nullptr};
   const int bcf_F = std::max(1, pl.n_format);
-  int size_kernel = 0;
   const uint64_t size2_units = (uint64_t)((P + kSizeBlock - 1) / kSizeBlock) * (uint64_t)nchunks;
   if (asm_path != 0 && size2_units >= (1ull << 31)) throw GenomicsDBDeviceException("more than 2^31 (record block, sample chunk) units in one interval: split the query interval");
-  const int frun = fill_run_length();
   const unsigned fill_units = (unsigned)(((P + frun - 1) / frun) * nchunks);
   if (pl.bcf_mode) {
     // BCF2: resolve the (record, sample) matrix, reduce the entries' summaries to vector length + type per (record, field), size the records
     if (asm_path == 2) {   // (k_size2 for the walkers' starting points; its text sizes mean nothing here)
       hipLaunchKernelGGL(k_size2, dim3((unsigned)size2_units), dim3(kAsmRows), 0, st, pc2, nchunks, S.chunk_size.p);
-      size_kernel = kSizeKernelPieces;
       hipLaunchKernelGGL(k_fill2, dim3(fill_units), dim3(kAsmRows), 0, st, pc2, (const uint2*)S.slot_desc.p, (const int32_t*)S.order.p, P, nchunks, frun, S.resolved.p, (int64_t)0);
     } else
-    size_kernel = launch_assemble_size(S, st, dim3(run_blocks * (unsigned)nchunks), ac, S.order.p, P, N, nchunks, run, (uint64_t*)nullptr, 0, res_view(), (int64_t)0, (int64_t)0);
+    launch_assemble_size(S, st, sz.size_kernel, size_grid, ac, S.order.p, P, N, nchunks, run, (uint64_t*)nullptr, 0, S.res_view(), (int64_t)0, (int64_t)0);
     S.bcf_part.ensure(nchunk_total * (size_t)bcf_F + 1); S.bcf_fmeta.ensure((size_t)P * bcf_F + 1); S.bcf_foff.ensure((size_t)P * bcf_F + 1); S.bcf_lindiv.ensure((size_t)P + 1);
     S.bcf_rec_size.ensure((size_t)P + 2);
     lay = BcfLayout{S.bcf_fmeta.p, S.bcf_foff.p, S.bcf_lindiv.p, S.bcf_rec_size.p};
     STAGE("k_bcf_field_meta");
-    hipLaunchKernelGGL(k_bcf_field_meta, dim3((unsigned)(((P + kBcfRun - 1) / kBcfRun) * nchunks)), dim3(kAsmRows), 0, st, res_view(), (const char*)S.pool.p,
+    hipLaunchKernelGGL(k_bcf_field_meta, dim3((unsigned)(((P + kBcfRun - 1) / kBcfRun) * nchunks)), dim3(kAsmRows), 0, st, S.res_view(), (const char*)S.pool.p,
                        (const char*)S.pool_ovf.p, (const uint32_t*)S.fmt_mask.p, (const int32_t*)S.order.p, P, nchunks, bcf_F, S.bcf_part.p);
     hipLaunchKernelGGL(k_bcf_layout, dim3(blocks_for(P)), dim3(kBlock), 0, st, pl, (const uint32_t*)S.bcf_part.p, (const uint32_t*)S.fmt_mask.p, (const uint32_t*)S.prefix_len.p, P,
                        nchunks, bcf_F, lay);
@@ -5943,21 +5880,17 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     S.excl_scan(S.bcf_rec_size.p, S.rec_off.p, (size_t)P + 1);
     hipLaunchKernelGGL(k_bcf_max_record, dim3(blocks_for(P)), dim3(kBlock), 0, st, (const uint64_t*)S.bcf_rec_size.p, P, S.max_record.p);
   } else {
-  const int evrun = event_run_length();
-  const uint64_t ev_blocks = (uint64_t)((P + evrun - 1) / evrun) * (uint64_t)nchunks;
-  use_events = events_enabled() && ev_blocks * (uint64_t)evrun * kAsmRows * sizeof(uint2) <= resolved_budget_bytes() && ((1 << order_block_log2()) % evrun) == 0;
-  if (use_events) {
+  if (sz.use_events) {
+    const uint64_t ev_blocks = (uint64_t)((P + evrun - 1) / evrun) * (uint64_t)nchunks;
     // sizing pass that leaves the change list of every (run, chunk) instead of the dense matrix
     S.ev_init.ensure((size_t)ev_blocks * kAsmRows); S.ev_buf.ensure((size_t)ev_blocks * evrun * kAsmRows); S.ev_count.ensure((size_t)ev_blocks);
-    ebuf = EventBuf{S.ev_init.p, S.ev_buf.p, S.ev_count.p, evrun};
+    const EventBuf ebuf = S.iv.eb = EventBuf{S.ev_init.p, S.ev_buf.p, S.ev_count.p, evrun};
     hipLaunchKernelGGL(k_assemble_size_ev, dim3((unsigned)ev_blocks), dim3(kAsmRows), 0, st, ac, S.order.p, P, N, nchunks, evrun, S.chunk_size.p, ebuf, S.err.p);
-    size_kernel = kSizeKernelEvents;
     S.order_iv.ensure((size_t)P);
     HIP_CHECK(hipMemcpyAsync(S.order_iv.p, S.order.p, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     S.order_iv_valid = true;
   } else if (asm_path != 0) {
     hipLaunchKernelGGL(k_size2, dim3((unsigned)size2_units), dim3(kAsmRows), 0, st, pc2, nchunks, S.chunk_size.p);
-    size_kernel = kSizeKernelPieces;
     if (asm_path == 3) {   // piece lists: count, offsets, fill
       const size_t nlists = (size_t)((P + kSizeBlock - 1) / kSizeBlock) * (size_t)ntypes * (size_t)N;
       S.pl_cnt.ensure(nlists + 1); S.pl_ofs.ensure(nlists + 1);
@@ -5969,10 +5902,10 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
       hipLaunchKernelGGL(k_plist<true>, dim3((unsigned)size2_units), dim3(kAsmRows), 0, st, pc2, (const uint2*)S.slot_desc.p, ntypes, nchunks, S.pl_ofs.p, S.plist.p);
       S.iv.NT = ntypes;
     }
-    if (asm_path == 2 && resolved_whole)
+    if (asm_path == 2 && sz.resolved_whole)
       hipLaunchKernelGGL(k_fill2, dim3(fill_units), dim3(kAsmRows), 0, st, pc2, (const uint2*)S.slot_desc.p, (const int32_t*)S.order.p, P, nchunks, frun, S.resolved.p, (int64_t)0);
   } else
-  size_kernel = launch_assemble_size(S, st, dim3(run_blocks * (unsigned)nchunks), ac, S.order.p, P, N, nchunks, run, S.chunk_size.p, nchunk_total, resolved_whole ? res_view() : ResMatrix{nullptr, nullptr, nullptr}, (int64_t)0, res_chunk_major() ? P : (int64_t)0);
+  launch_assemble_size(S, st, sz.size_kernel, size_grid, ac, S.order.p, P, N, nchunks, run, S.chunk_size.p, nchunk_total, sz.resolved_whole ? S.res_view() : ResMatrix{nullptr, nullptr, nullptr}, (int64_t)0, sz.res_rows(P));
   HIP_CHECK(hipMemsetAsync(S.chunk_size.p + nchunk_total, 0, sizeof(uint64_t), st));
   S.excl_scan(S.chunk_size.p, S.chunk_off.p, nchunk_total + 1);
   STAGE("k_gather_record_offsets");
@@ -5994,10 +5927,8 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   if (eb) throw GenomicsDBDeviceException(err_bits_text(eb));
   S.iv.max_record_bytes = totals[1]; S.iv.total_bytes = totals[0];
   S.iv.P = P; S.iv.nchunks = nchunks; S.iv.kp = 0;
-  S.iv.sx = sx; S.iv.ex = ex; S.iv.ri = ri; S.iv.so = so; S.iv.rec = rec; S.iv.ac = ac; S.iv.pc2 = pc2; S.iv.piece_path = piece_path; S.iv.asm_path = asm_path; S.iv.resolved_whole = resolved_whole; S.iv.res_compact = res_compact; S.iv.P_rows = P;
-  S.iv.bcf = pl.bcf_mode != 0; S.iv.bcf_F = bcf_F; S.iv.lay = lay;
-  S.iv.events = use_events; S.iv.evrun = ebuf.run; S.iv.eb = ebuf;
-  S.iv.size_kernel = size_kernel;
+  S.iv.sx = sx; S.iv.ex = ex; S.iv.ri = ri; S.iv.so = so; S.iv.rec = rec; S.iv.ac = ac; S.iv.pc2 = pc2;
+  S.iv.bcf_F = bcf_F; S.iv.lay = lay;
   S.iv.active = true;
 }
 
@@ -6013,6 +5944,8 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
   hipStream_t st = S.stream;
   const int ai = arena_idx & 1;
   const int32_t N = S.hp.plan.num_query_rows;
+  const AssemblySizing& sz = iv.sz;
+  // ---- 1. extent: as many whole records as fit the arena ----------------------------------------------------------------
   const uint64_t arena_cap = std::max<uint64_t>(arena_bytes, iv.max_record_bytes);
   const int64_t kp = iv.kp, P = iv.P;
   int64_t ke = P;
@@ -6024,17 +5957,11 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
       HIP_CHECK(hipMemcpyAsync(rec_off.data(), S.rec_off.p, (size_t)(P + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
     }
-    int64_t lo = kp + 1, hi = P;  // largest k_end with rec_off[k_end] - rec_off[kp] <= arena_cap
-    while (lo < hi) { int64_t mid = (lo + hi + 1) >> 1; if (rec_off[(size_t)mid] - rec_off[(size_t)kp] <= arena_cap) lo = mid; else hi = mid - 1; }
-    ke = lo;
-    // the change list is laid out over the interval's order blocks: a page that ends on a block boundary can use it as it is
-    if (iv.events && !iv.bcf) {
-      const int64_t blk = (int64_t)1 << order_block_log2();
-      if (ke < P && (kp % blk) == 0 && (ke / blk) * blk > kp) ke = (ke / blk) * blk;
-    }
+    ke = page_end(iv.knobs, sz, rec_off.data(), kp, P, arena_cap);
     page_base = rec_off[(size_t)kp];
     page_bytes = rec_off[(size_t)ke] - page_base;
   }
+  // ---- 2. arena -------------------------------------------------------------------------------------------------------------
   if (S.arena_release[ai]) { HIP_CHECK(hipStreamWaitEvent(st, S.arena_release[ai], 0)); S.arena_release[ai] = nullptr; }
   if (S.arena[ai].cap < (S.hp.bgzf ? bgzf_bound(page_bytes) : page_bytes) + 64) {   // (re)allocation frees memory a copy may still read: the stream has to be idle
     HIP_CHECK(hipStreamSynchronize(st));
@@ -6042,12 +5969,53 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
     S.arena[ai].ensure((S.hp.bgzf ? bgzf_bound(want) : want) + 64);      // (a page of incompressible bytes grows by the block framing)
   }
   char* const arena = S.arena[ai].p;
+  // ---- 3. the kernels choose_page names: site columns, order, (matrix of this page's records), the page kernel --------------
+  const PageChoice pc = choose_page(iv.knobs, sz, kp, ke, P, iv.nchunks, iv.total_bytes, iv.max_record_bytes, S.order_iv_valid);
+  iv.stats.page_kernel = pc.code;
   const int64_t np = ke - kp;
+  const int wrun = pc.run, nchunks = iv.nchunks;
+  const unsigned units = (unsigned)((np + wrun - 1) / wrun) * (unsigned)nchunks;   // (run, chunk) pairs: one wavefront each
+  const dim3 wgrid((units + (unsigned)pc.waves - 1u) / (unsigned)pc.waves), wblock(kAsmRows * pc.waves);
+  const int xcd_aware = iv.knobs.xcd_aware ? 1 : 0;
+  // the <waves, image> instantiation choose_page named, out of those a kernel template has: picked before anything is enqueued
+#define GDB_INSTANCE(KERNEL, W, L) pc.waves == (W) && pc.lds_bytes == (L) ? KERNEL<W, L> :
+  const auto k_write = pc.kernel != kPageKernelWrite ? nullptr : pc.coop_u == 4 ? k_assemble_write<1, 8192, 4> :
+                       GDB_INSTANCE(k_assemble_write, 4, 4096) GDB_INSTANCE(k_assemble_write, 4, 6144) GDB_INSTANCE(k_assemble_write, 4, 8192) GDB_INSTANCE(k_assemble_write, 2, 4096)
+                       GDB_INSTANCE(k_assemble_write, 2, 8192) GDB_INSTANCE(k_assemble_write, 1, 4096) GDB_INSTANCE(k_assemble_write, 1, 8192) nullptr;
+  const auto k_w2 = pc.kernel != kPageKernelWrite2 ? nullptr :
+                    GDB_INSTANCE(k_write2, 4, 4096) GDB_INSTANCE(k_write2, 4, 8192) GDB_INSTANCE(k_write2, 1, 4096) GDB_INSTANCE(k_write2, 1, 6144) GDB_INSTANCE(k_write2, 1, 8192) nullptr;
+  const auto k_w3 = pc.kernel != kPageKernelWrite3 ? nullptr : GDB_INSTANCE(k_write3, 1, 4096) GDB_INSTANCE(k_write3, 1, 8192) nullptr;
+#undef GDB_INSTANCE
+  if (pc.kernel >= kPageKernelWrite && pc.kernel <= kPageKernelWrite3 && !k_write && !k_w2 && !k_w3) throw GenomicsDBDeviceException("begin_page: choose_page named a kernel instantiation that does not exist");
   hipEvent_t* w = S.ev_page[ai];
   HIP_CHECK(hipEventRecord(w[0], st));
+  if (sz.bcf_mode) {
+    STAGE("k_bcf_shared");
+    hipLaunchKernelGGL(k_bcf_shared, dim3(blocks_for(np, 64)), dim3(64), 0, st, S.d_sx.p, (const char*)S.site_staging.p, (const char*)S.spill_buf.p, (const int32_t*)S.spill_chunk.p, kp, ke,
+                       (const uint64_t*)S.rec_off.p, page_base, iv.lay, iv.bcf_F, arena, S.err.p);
+    STAGE("k_bcf_write");
+  } else {
+    STAGE("k_site_write");
+    hipLaunchKernelGGL(k_site_copy, dim3(blocks_for(np, 4)), dim3(256), 0, st, (const uint32_t*)S.prefix_len.p, (const char*)S.site_staging.p, (const char*)S.spill_buf.p, (const int32_t*)S.spill_chunk.p, kp, ke,
+                       (const uint64_t*)S.chunk_off.p, nchunks, page_base, arena);
+    hipLaunchKernelGGL(k_site_write, dim3(blocks_for(np, 64)), dim3(64), 0, st, S.d_sx.p, (const char*)S.site_staging.p, (const char*)S.spill_buf.p, (const int32_t*)S.spill_chunk.p, kp, ke, S.chunk_off.p, nchunks, page_base, arena, S.err.p);
+    STAGE("k_assemble_write");
+  }
+  if (pc.kernel != kPageKernelEvents) S.order_by_type(kp, np, iv.knobs.order_block_log2);   // (the change list keeps the interval's order: order_iv)
+  if (sz.bcf_mode) {
+    S.bcf_same.ensure((size_t)np + 1);
+    hipLaunchKernelGGL(k_bcf_same_layout, dim3(blocks_for(np)), dim3(kBlock), 0, st, (const int32_t*)S.order.p, (const uint32_t*)S.fmt_mask.p, (const uint32_t*)iv.lay.fmeta, np, iv.bcf_F, S.bcf_same.p);
+  }
+  if (pc.resolve_kernel >= 0) {   // the interval's matrix exceeded the budget: resolve this page's records now
+    if (sz.res_compact) { S.res_off.ensure((size_t)np * nchunks * kAsmRows); S.res_len8.ensure((size_t)np * nchunks * kAsmRows); }
+    else S.resolved.ensure((size_t)np * nchunks * kAsmRows);
+    if (pc.resolve_kernel == kSizeKernelPieces)
+      hipLaunchKernelGGL(k_fill2, dim3((unsigned)(((np + sz.frun - 1) / sz.frun) * nchunks)), dim3(kAsmRows), 0, st, iv.pc2, (const uint2*)S.slot_desc.p, (const int32_t*)S.order.p, np, nchunks, sz.frun, S.resolved.p, kp);
+    else launch_assemble_size(S, st, pc.resolve_kernel, dim3(units), iv.ac, S.order.p, np, N, nchunks, wrun, (uint64_t*)nullptr, 0, S.res_view(), kp, pc.res_rows);
+  }
   // the stream of the page kernel: the compute stream, or (several windows in flight) a high-priority one forked from it and joined behind the kernel
-  const auto fork_page_stream = [&S, st]() -> hipStream_t {
-    if (!(page_priority_env() >= 0 ? page_priority_env() == 1 : S.page_priority)) return st;
+  hipStream_t st_w = st;
+  if (pc.forks && iv.knobs.page_priority_on(S.page_priority)) {
     if (!S.stream_page) {
       int least = 0, greatest = 0;
       HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -6057,139 +6025,48 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
     }
     HIP_CHECK(hipEventRecord(S.ev_page_fork, st));
     HIP_CHECK(hipStreamWaitEvent(S.stream_page, S.ev_page_fork, 0));
-    return S.stream_page;
-  };
-  const auto join_page_stream = [&S, st](hipStream_t st_w) { if (st_w != st) { HIP_CHECK(hipEventRecord(S.ev_page_join, st_w)); HIP_CHECK(hipStreamWaitEvent(st, S.ev_page_join, 0)); } };
-  if (iv.bcf) {
-    STAGE("k_bcf_shared");
-    hipLaunchKernelGGL(k_bcf_shared, dim3(blocks_for(np, 64)), dim3(64), 0, st, S.d_sx.p, (const char*)S.site_staging.p, (const char*)S.spill_buf.p, (const int32_t*)S.spill_chunk.p, kp, ke,
-                       (const uint64_t*)S.rec_off.p, page_base, iv.lay, iv.bcf_F, arena, S.err.p);
-    STAGE("k_bcf_write");
-    S.order_by_type(kp, np);
-    S.bcf_same.ensure((size_t)np + 1);
-    hipLaunchKernelGGL(k_bcf_same_layout, dim3(blocks_for(np)), dim3(kBlock), 0, st, (const int32_t*)S.order.p, (const uint32_t*)S.fmt_mask.p, (const uint32_t*)iv.lay.fmeta, np, iv.bcf_F, S.bcf_same.p);
-    const hipStream_t st_w = fork_page_stream();
-    HIP_CHECK(hipEventRecord(w[1], st_w));   // [w1, w2]: the values kernel alone
-    if (S.hp.plan.n_format > 0 && !S.hp.plan.sites_only_query)
-      hipLaunchKernelGGL(k_bcf_write, dim3((unsigned)(((np + kBcfRun - 1) / kBcfRun) * iv.nchunks)), dim3(kAsmRows), 0, st_w, S.hp.plan, iv.res_compact ? ResMatrix{nullptr, S.res_off.p, S.res_len8.p} : ResMatrix{S.resolved.p, nullptr, nullptr}, (const char*)S.pool.p,
-                         (const char*)S.pool_ovf.p, (const uint32_t*)S.fmt_mask.p, (const int32_t*)S.order.p, (const uint8_t*)S.bcf_same.p, np, iv.nchunks, iv.bcf_F, N, iv.lay, (const uint64_t*)S.rec_off.p, page_base, arena BCF_PROF_ARG);
-    iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelBcf, 1, 0, 0);
+    st_w = S.stream_page;
+  }
+  HIP_CHECK(hipEventRecord(w[1], st_w));   // [w1, w2] brackets the page kernel alone (its duration feeds the roofline figure)
+  const char* const pool = S.pool.p; const char* const pool_ovf = S.pool_ovf.p; const int32_t* const order = S.order.p; const uint64_t* const chunk_off = S.chunk_off.p;
+  switch (pc.kernel) {
+    case kPageKernelBcf:
+      if (S.hp.plan.n_format > 0 && !S.hp.plan.sites_only_query)
+        hipLaunchKernelGGL(k_bcf_write, dim3((unsigned)(((np + kBcfRun - 1) / kBcfRun) * nchunks)), dim3(kAsmRows), 0, st_w, S.hp.plan, S.res_view(), pool, pool_ovf, (const uint32_t*)S.fmt_mask.p, order,
+                           (const uint8_t*)S.bcf_same.p, np, nchunks, iv.bcf_F, N, iv.lay, (const uint64_t*)S.rec_off.p, page_base, arena BCF_PROF_ARG);
 #ifdef GDB_BCF_PROF
-    { unsigned long long h[12]; HIP_CHECK(hipStreamSynchronize(st_w)); HIP_CHECK(hipMemcpy(h, bcf_prof_buffer(), sizeof h, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemset(bcf_prof_buffer(), 0, sizeof h));
-      fprintf(stderr, "k_bcf_write cycles per step (100 MHz ticks x wavefronts / steps): top %.1f layout %.1f lanes-pass %.1f groups %.1f flush %.1f slow %.1f; steps %llu, with group passes %llu\n", (double)h[0] / h[8], (double)h[1] / h[8],
-              (double)h[2] / h[8], (double)h[3] / h[8], (double)h[4] / h[8], (double)h[5] / h[8], h[8], h[9]); }
+      { unsigned long long h[12]; HIP_CHECK(hipStreamSynchronize(st_w)); HIP_CHECK(hipMemcpy(h, bcf_prof_buffer(), sizeof h, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemset(bcf_prof_buffer(), 0, sizeof h));
+        fprintf(stderr, "k_bcf_write cycles per step (100 MHz ticks x wavefronts / steps): top %.1f layout %.1f lanes-pass %.1f groups %.1f flush %.1f slow %.1f; steps %llu, with group passes %llu\n", (double)h[0] / h[8], (double)h[1] / h[8],
+                (double)h[2] / h[8], (double)h[3] / h[8], (double)h[4] / h[8], (double)h[5] / h[8], h[8], h[9]); }
 #endif
-    HIP_CHECK(hipEventRecord(w[2], st_w));
-    join_page_stream(st_w);
-    HIP_CHECK(hipMemcpyAsync(&S.hb->page_err[ai], S.err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(w[3], st));
-    iv.kp = ke;
-    ticket->arena = ai; ticket->dev = arena; ticket->nbytes = page_bytes; ticket->done_event = (void*)w[3]; S.queue_compression(ai, arena, page_bytes);
-    return true;
-  }
-  STAGE("k_site_write");
-  hipLaunchKernelGGL(k_site_copy, dim3(blocks_for(np, 4)), dim3(256), 0, st, (const uint32_t*)S.prefix_len.p, (const char*)S.site_staging.p, (const char*)S.spill_buf.p, (const int32_t*)S.spill_chunk.p, kp, ke,
-                     (const uint64_t*)S.chunk_off.p, iv.nchunks, page_base, arena);
-  hipLaunchKernelGGL(k_site_write, dim3(blocks_for(np, 64)), dim3(64), 0, st, S.d_sx.p, (const char*)S.site_staging.p, (const char*)S.spill_buf.p, (const int32_t*)S.spill_chunk.p, kp, ke, S.chunk_off.p, iv.nchunks, page_base, arena, S.err.p);
-  STAGE("k_assemble_write");
-  {
-    const int64_t blk = (int64_t)1 << order_block_log2();
-    if (iv.events && S.order_iv_valid && (kp % blk) == 0 && (ke == P || (ke % blk) == 0)) {
-      const int evrun = iv.evrun;
-      const unsigned eruns = (unsigned)((np + evrun - 1) / evrun);
-      HIP_CHECK(hipEventRecord(w[1], st));
-      const unsigned units = eruns * (unsigned)iv.nchunks;
-      if (write_waves_per_group() >= 4) {
-        iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelEvents, 4, 0, kWaveLds);
-        hipLaunchKernelGGL(k_assemble_write_ev<4>, dim3((units + 3u) / 4u), dim3(kAsmRows * 4), 0, st, (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const uint32_t*)S.prefix_len.p,
-                           iv.eb, (int64_t)(kp / evrun) * iv.nchunks, (const int32_t*)(S.order_iv.p + kp), np, iv.nchunks, evrun, (const uint64_t*)S.chunk_off.p, page_base, arena);
-      } else {
-        iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelEvents, 1, 0, kWaveLds);
-        hipLaunchKernelGGL(k_assemble_write_ev<1>, dim3(units), dim3(kAsmRows), 0, st, (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const uint32_t*)S.prefix_len.p,
-                           iv.eb, (int64_t)(kp / evrun) * iv.nchunks, (const int32_t*)(S.order_iv.p + kp), np, iv.nchunks, evrun, (const uint64_t*)S.chunk_off.p, page_base, arena);
+      break;
+    case kPageKernelEvents:
+      hipLaunchKernelGGL(pc.waves == 4 ? k_assemble_write_ev<4> : k_assemble_write_ev<1>, wgrid, wblock, 0, st_w, pool, pool_ovf, (const uint32_t*)S.prefix_len.p, iv.eb, (int64_t)(kp / wrun) * nchunks,
+                         (const int32_t*)(S.order_iv.p + kp), np, nchunks, wrun, chunk_off, page_base, arena);
+      break;
+    case kPageKernelWrite2: case kPageKernelWrite3: {   // matrix-free: the page kernel walks the pieces (k_write2) or reads their lists (k_write3)
+      const int w2dbg = getenv("GDBAMD_W2_DBG") ? atoi(getenv("GDBAMD_W2_DBG")) : 0;
+      S.dbg_counters.ensure(8);
+      if (w2dbg & 64) HIP_CHECK(hipMemsetAsync(S.dbg_counters.p, 0, 8 * sizeof(unsigned long long), st));
+      if (k_w2) hipLaunchKernelGGL(k_w2, wgrid, wblock, 0, st_w, iv.pc2, pool, pool_ovf, order, np, nchunks, wrun, chunk_off, page_base, arena, xcd_aware | (w2dbg << 1));
+      else hipLaunchKernelGGL(k_w3, wgrid, wblock, 0, st_w, iv.pc2, (const PieceEntry*)S.plist.p, (const uint32_t*)S.pl_ofs.p, iv.NT, pool, pool_ovf, order, np, nchunks, wrun, chunk_off, page_base, arena,
+                              xcd_aware | (w2dbg << 1), S.dbg_counters.p);
+      if ((w2dbg & 64) && pc.kernel == kPageKernelWrite3) {
+        unsigned long long c[4];
+        HIP_CHECK(hipMemcpyAsync(c, S.dbg_counters.p, sizeof(c), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        fprintf(stderr, "[k_write3] wavefront cycles %.3e, waiting for texts %.3e (%.1f %%), waits %llu, steps %llu: %.0f cycles per step, %.0f per wait\n", (double)c[0], (double)c[1],
+                100.0 * (double)c[1] / (double)std::max<unsigned long long>(1, c[0]), c[2], c[3], (double)c[0] / (double)std::max<unsigned long long>(1, c[3]), (double)c[1] / (double)std::max<unsigned long long>(1, c[2]));
       }
-      HIP_CHECK(hipEventRecord(w[2], st));
-      HIP_CHECK(hipMemcpyAsync(&S.hb->page_err[ai], S.err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipEventRecord(w[3], st));
-      iv.kp = ke;
-      ticket->arena = ai; ticket->dev = arena; ticket->nbytes = page_bytes; ticket->done_event = (void*)w[3]; S.queue_compression(ai, arena, page_bytes);
-      return true;
+      break;
     }
+    default:   // kPageKernelWrite
+      hipLaunchKernelGGL(k_write, wgrid, wblock, 0, st_w, pool, pool_ovf, (const uint32_t*)S.prefix_len.p, S.res_view(), sz.resolved_whole ? (int64_t)0 : kp, order, np, nchunks, wrun, chunk_off, page_base, arena,
+                         xcd_aware, pc.res_rows);
   }
-  const int wrun = iv.piece_path ? write2_run_length() : write_run_length();
-  S.order_by_type(kp, np);
-  const unsigned wruns = (unsigned)((np + wrun - 1) / wrun);
-  const dim3 wgrid(wruns * (unsigned)iv.nchunks);
-  if (iv.piece_path) {
-    HIP_CHECK(hipEventRecord(w[1], st));
-#define GDB_LAUNCH_WRITE2(W, L) do { iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite2, W, 0, L); hipLaunchKernelGGL((k_write2<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st, iv.pc2, (const char*)S.pool.p, (const char*)S.pool_ovf.p, \
-    (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, (xcd_aware_numbering() ? 1 : 0) | (w2dbg << 1)); } while (0)
-    const int ww = write_waves_per_group(), wl = write_image_kb(iv.P > 0 && iv.nchunks > 0 ? iv.total_bytes / ((uint64_t)iv.P * (uint64_t)iv.nchunks) : 0);
-    const int w2dbg = getenv("GDBAMD_W2_DBG") ? atoi(getenv("GDBAMD_W2_DBG")) : 0;
-    S.dbg_counters.ensure(8);
-    if (w2dbg & 64) HIP_CHECK(hipMemsetAsync(S.dbg_counters.p, 0, 8 * sizeof(unsigned long long), st));
-#define GDB_LAUNCH_WRITE3(W, L) do { iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite3, W, 0, L); hipLaunchKernelGGL((k_write3<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st, iv.pc2, (const PieceEntry*)S.plist.p, (const uint32_t*)S.pl_ofs.p, iv.NT, \
-    (const char*)S.pool.p, (const char*)S.pool_ovf.p, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, (xcd_aware_numbering() ? 1 : 0) | (w2dbg << 1), S.dbg_counters.p); } while (0)
-    if (iv.asm_path == 3) { if (wl <= 4) GDB_LAUNCH_WRITE3(1, 4096); else GDB_LAUNCH_WRITE3(1, 8192); }
-    else
-    if (ww >= 4 && wl <= 4) GDB_LAUNCH_WRITE2(4, 4096);
-    else if (ww >= 4) GDB_LAUNCH_WRITE2(4, 8192);
-    else if (wl <= 4) GDB_LAUNCH_WRITE2(1, 4096);
-    else if (wl <= 6) GDB_LAUNCH_WRITE2(1, 6144);
-    else GDB_LAUNCH_WRITE2(1, 8192);
-#undef GDB_LAUNCH_WRITE2
-#undef GDB_LAUNCH_WRITE3
-    if ((w2dbg & 64) && iv.asm_path == 3) {
-      unsigned long long c[4];
-      HIP_CHECK(hipMemcpyAsync(c, S.dbg_counters.p, sizeof(c), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-      fprintf(stderr, "[k_write3] wavefront cycles %.3e, waiting for texts %.3e (%.1f %%), waits %llu, steps %llu: %.0f cycles per step, %.0f per wait\n", (double)c[0], (double)c[1],
-              100.0 * (double)c[1] / (double)std::max<unsigned long long>(1, c[0]), c[2], c[3], (double)c[0] / (double)std::max<unsigned long long>(1, c[3]), (double)c[1] / (double)std::max<unsigned long long>(1, c[2]));
-    }
-    HIP_CHECK(hipEventRecord(w[2], st));
-    HIP_CHECK(hipMemcpyAsync(&S.hb->page_err[ai], S.err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(w[3], st));
-    iv.kp = ke;
-    ticket->arena = ai; ticket->dev = arena; ticket->nbytes = page_bytes; ticket->done_event = (void*)w[3]; S.queue_compression(ai, arena, page_bytes);
-    return true;
-  }
-  const auto res_view = [&S, &iv]() { return iv.res_compact ? ResMatrix{nullptr, S.res_off.p, S.res_len8.p} : ResMatrix{S.resolved.p, nullptr, nullptr}; };
-  if (!iv.resolved_whole) {   // the interval's matrix exceeded the budget: resolve this page's records now
-    if (iv.res_compact) { S.res_off.ensure((size_t)np * iv.nchunks * kAsmRows); S.res_len8.ensure((size_t)np * iv.nchunks * kAsmRows); }
-    else S.resolved.ensure((size_t)np * iv.nchunks * kAsmRows);
-    if (iv.asm_path == 2) {
-      const int frun = fill_run_length();
-      hipLaunchKernelGGL(k_fill2, dim3((unsigned)(((np + frun - 1) / frun) * iv.nchunks)), dim3(kAsmRows), 0, st, iv.pc2, (const uint2*)S.slot_desc.p, (const int32_t*)S.order.p, np, iv.nchunks, frun,
-                         S.resolved.p, kp);
-    } else
-    launch_assemble_size(S, st, wgrid, iv.ac, S.order.p, np, N, iv.nchunks, wrun, (uint64_t*)nullptr, 0, res_view(), kp, res_chunk_major() && iv.asm_path != 2 ? np : (int64_t)0);
-  }
-  const hipStream_t st_w = fork_page_stream();
-  HIP_CHECK(hipEventRecord(w[1], st_w));   // [w1, w2] brackets the page-assembly kernel alone (its duration feeds the roofline figure)
-#define GDB_LAUNCH_WRITE(W, L) do { iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite, W, 2, L); hipLaunchKernelGGL((k_assemble_write<W, L>), dim3((wgrid.x + (W) - 1u) / (W)), dim3(kAsmRows * (W)), 0, st_w, (const char*)S.pool.p, (const char*)S.pool_ovf.p, \
-    (const uint32_t*)S.prefix_len.p, res_view(), iv.resolved_whole ? (int64_t)0 : kp, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, xcd_aware_numbering() ? 1 : 0, \
-    (res_chunk_major() && iv.asm_path != 2) ? (iv.resolved_whole ? (int64_t)iv.P_rows : np) : (int64_t)0); } while (0)
-  {
-    const int ww = write_waves_per_group(), wl = write_image_kb(iv.P > 0 && iv.nchunks > 0 ? iv.total_bytes / ((uint64_t)iv.P * (uint64_t)iv.nchunks) : 0);
-    // the largest record's average entry is a long one (copied by the whole wavefront): the variant that keeps 4 words per lane in flight
-    const bool long_entries = coop_unroll_wanted() && iv.nchunks > 0 && iv.max_record_bytes / ((uint64_t)iv.nchunks * kAsmRows) > (uint64_t)kCooperativeEntry;
-    if (long_entries && ww == 1) {
-      iv.stats.page_kernel = page_kernel_code(iv.size_kernel, kPageKernelWrite, 1, 4, 8192);
-      hipLaunchKernelGGL((k_assemble_write<1, 8192, 4>), dim3(wgrid.x), dim3(kAsmRows), 0, st_w, (const char*)S.pool.p, (const char*)S.pool_ovf.p,
-        (const uint32_t*)S.prefix_len.p, res_view(), iv.resolved_whole ? (int64_t)0 : kp, (const int32_t*)S.order.p, np, iv.nchunks, wrun, (const uint64_t*)S.chunk_off.p, page_base, arena, xcd_aware_numbering() ? 1 : 0,
-        (res_chunk_major() && iv.asm_path != 2) ? (iv.resolved_whole ? (int64_t)iv.P_rows : np) : (int64_t)0);
-    } else
-    if (ww >= 4 && wl <= 4) GDB_LAUNCH_WRITE(4, 4096);
-    else if (ww >= 4 && wl <= 6) GDB_LAUNCH_WRITE(4, 6144);
-    else if (ww >= 4) GDB_LAUNCH_WRITE(4, 8192);
-    else if (ww == 2 && wl <= 4) GDB_LAUNCH_WRITE(2, 4096);
-    else if (ww == 2) GDB_LAUNCH_WRITE(2, 8192);
-    else if (wl <= 4) GDB_LAUNCH_WRITE(1, 4096);
-    else GDB_LAUNCH_WRITE(1, 8192);
-  }
-#undef GDB_LAUNCH_WRITE
+  // ---- 4. epilogue --------------------------------------------------------------------------------------------------------
   HIP_CHECK(hipEventRecord(w[2], st_w));
-  join_page_stream(st_w);
+  if (st_w != st) { HIP_CHECK(hipEventRecord(S.ev_page_join, st_w)); HIP_CHECK(hipStreamWaitEvent(st, S.ev_page_join, 0)); }
   HIP_CHECK(hipMemcpyAsync(&S.hb->page_err[ai], S.err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipEventRecord(w[3], st));
   iv.kp = ke;
