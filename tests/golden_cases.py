@@ -78,7 +78,63 @@ UNCOVERED = {
 }
 
 
-# ---- gt_mpi_gather --print-calls (the reference's "calls" goldens, tests/run.py:184-720) ----------------------------------------
+# ---- the reference's java_vcf goldens: htsjdk's text of the BCF2 stream GenomicsDBFeatureReader opens -----------------------------------
+# (reference tests/run.py:184-870; run.py:947 gives java_vcf the vcf_attributes_order like vcf.)  The stream is opened with is_bcf,
+# use_missing_values_only_not_vector_end and without IDX keys (GenomicsDBQueryStream.java:39-41) and printed by tests/tools/htsjdk_text.py.
+# The reference's spark_* goldens belong to its Spark input format and differ from their twins in the #CHROM line: out of scope.
+ASA_VCF_ATTRIBUTES = VCF_ATTRIBUTES_ORDER + ["AS_RAW_MQ", "AS_RAW_MQRankSum"]      # run.py:55 (asa_vcf_attributes)
+
+JAVA_CASES = [
+    # name, callsets, vid, query overrides, java golden, C++ text twin (a golden of the same query, None when the reference has none)
+    ("java_t0_1_2_vcf_at_0", "t0_1_2.json", "vid.json", {"query_column_ranges": FULL}, "java_t0_1_2_vcf_at_0", "t0_1_2_vcf_at_0"),
+    ("java_t0_1_2_vcf_at_0_phased_GT_vid", "t0_1_2.json", "vid_phased_GT.json", {"query_column_ranges": FULL}, "java_t0_1_2_vcf_at_0",
+     "t0_1_2_vcf_at_0"),
+    ("java_t0_1_2_vcf_at_multiple_positions", "t0_1_2.json", "vid.json",
+     {"query_column_ranges": [[12000, 12142, 12144, 12160, 12290, 12294, 14000, 17384, 18000]]},
+     "java_t0_1_2_vcf_at_multiple_positions", "t0_1_2_vcf_at_multiple_positions"),
+    ("java_t0_1_2_vcf_sites_only_at_0", "t0_1_2.json", "vid.json", {"query_column_ranges": FULL, "sites_only_query": True},
+     "java_t0_1_2_vcf_sites_only_at_0", "t0_1_2_vcf_sites_only_at_0"),
+    ("java_t0_1_2_vcf_at_12150", "t0_1_2.json", "vid.json", {"query_column_ranges": _r(12150)}, "java_t0_1_2_vcf_at_12150", "t0_1_2_vcf_at_12150"),
+    ("java_t6_7_8_vcf_at_0", "t6_7_8.json", "vid.json", {"query_column_ranges": FULL}, "java_t6_7_8_vcf_at_0", "t6_7_8_vcf_at_0"),
+    ("java_t6_7_8_vcf_at_8029500", "t6_7_8.json", "vid.json", {"query_column_ranges": _r(8029500)}, "java_t6_7_8_vcf_at_8029500",
+     "t6_7_8_vcf_at_8029500"),
+    ("java_t6_7_8_vcf_at_8029501", "t6_7_8.json", "vid.json", {"query_column_ranges": _r(8029501, 8029501)}, "java_t6_7_8_vcf_at_8029501", None),
+    (HT + "_java_vcf", HT + ".json", "vid_DS_ID_phased_GT.json", {"query_column_ranges": FULL}, HT + "_java_vcf", HT + "_vcf"),
+    (HT + "_java_vcf_produce_GT", HT + ".json", "vid_DS_ID_phased_GT.json", {"query_column_ranges": FULL, "produce_GT_field": True},
+     HT + "_java_vcf_produce_GT", HT + "_vcf_produce_GT"),
+    (HT + "_java_vcf_produce_GT_for_min_PL", HT + ".json", "vid_DS_ID_phased_GT.json",
+     {"query_column_ranges": FULL, "produce_GT_field": True, "produce_GT_with_min_PL_value_for_spanning_deletions": True},
+     HT + "_java_vcf_produce_GT_for_min_PL", HT + "_vcf_produce_GT_for_min_value_PL"),
+    (HT + "_java_vcf_sites_only", HT + ".json", "vid_DS_ID_phased_GT.json", {"query_column_ranges": FULL, "sites_only_query": True},
+     HT + "_java_vcf_sites_only", HT + "_vcf_sites_only"),
+    ("t0_1_2_all_asa_java_query_vcf", "t0_1_2_all_asa.json", "vid_all_asa.json", {"query_column_ranges": FULL, "attributes": ASA_VCF_ATTRIBUTES},
+     "t0_1_2_all_asa_java_query_vcf", "t0_1_2_all_asa_loading"),
+]
+
+# the rows the reference asks for as a contig interval (run.py:470-485): contig, 1-based begin, end - what GATK's query(chr, start, end)
+# passes to jniGenomicsDBInit.  The column interval of the same records is the row's own query.
+JAVA_CONTIG_INTERVALS = {
+    "java_t6_7_8_vcf_at_8029500": ("1", 8029501, 8029510),
+    "java_t6_7_8_vcf_at_8029501": ("1", 8029502, 8029502),
+}
+
+# goldens of a query over three arrays (run.py:337-365, chromosome_intervals 1:1-12160, 1:12161-12200, 1:12201-18000): one stream per
+# column partition, imported on its own and asked for the part of the query columns inside it (GenomicsDBFeatureIterator.java:114-118),
+# their records back to back under the first stream's header
+JAVA_MULTI_ARRAY_CASES = [
+    # name (= golden), callsets, vid, column partitions, query columns
+    ("java_genomicsdb_importer_from_vcfs_t0_1_2_multi_contig_vcf_0_18000", "t0_1_2.json", "vid_phased_GT.json",
+     [(0, 12159), (12160, 12199), (12200, 17999)], (0, 18000)),
+    ("java_genomicsdb_importer_from_vcfs_t0_1_2_multi_contig_vcf_12150_18000", "t0_1_2.json", "vid_phased_GT.json",
+     [(0, 12159), (12160, 12199), (12200, 17999)], (12150, 17999)),       # contig interval 1:12151-18000
+]
+
+# Java goldens that are NOT reproduced from the device's stream: name -> reason, with the first differing record
+JAVA_UNCOVERED = {
+}
+
+
+# ---- gt_mpi_gather --print-calls(the reference's "calls" goldens, tests/run.py:184-720) ----------------------------------------
 CALLS_ATTRIBUTES = ["REF", "ALT", "BaseQRankSum", "MQ", "RAW_MQ", "MQ0", "ClippingRankSum", "MQRankSum", "ReadPosRankSum", "DP", "GT", "GQ",
                     "SB", "AD", "PL", "DP_FORMAT", "MIN_DP", "PID", "PGT"]   # run.py:50 (the query template's "attributes")
 CALLS_ATTRIBUTES_DS_ID = CALLS_ATTRIBUTES + ["DS", "ID"]

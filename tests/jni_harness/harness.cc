@@ -49,8 +49,10 @@ jboolean f_ExceptionCheck(JNIEnv* e) { return static_cast<FakeEnv*>(e)->exceptio
 }  // namespace
 
 // returns 0 and the whole stream in *out (malloc'ed), or -1 with the pending "Java exception" text in err
-extern "C" int jni_harness_read_stream(const char* loader_json, const char* query_json, const char* chr, int start, int end, int is_bcf, int array_len, int use_read_next_byte_first,
-                                       unsigned char** out, unsigned long long* nbytes, char* err, unsigned long long err_cap) {
+// is_bcf, use_missing_values_only_not_vector_end, keep_idx_fields_in_bcf_header: the three flags GenomicsDBQueryStream.java passes to Init
+extern "C" int jni_harness_read_stream_flags(const char* loader_json, const char* query_json, const char* chr, int start, int end, int is_bcf,
+                                             int use_missing_values_only_not_vector_end, int keep_idx_fields_in_bcf_header, int array_len, int use_read_next_byte_first,
+                                             unsigned char** out, unsigned long long* nbytes, char* err, unsigned long long err_cap) {
   FakeEnv env;
   memset(&env.table, 0, sizeof(env.table));
   env.table.slot[6] = (void*)f_FindClass; env.table.slot[14] = (void*)f_ThrowNew; env.table.slot[169] = (void*)f_GetStringUTFChars;
@@ -61,7 +63,8 @@ extern "C" int jni_harness_read_stream(const char* loader_json, const char* quer
   if (Java_com_intel_genomicsdb_GenomicsDBLibLoader_jniGenomicsDBOneTimeInitialize(&env, nullptr) != 0) return fail("OneTimeInitialize != 0");
   FakeString l, q, c;
   l.s = loader_json ? loader_json : ""; q.s = query_json; c.s = chr ? chr : "";
-  const jlong h = Java_com_intel_genomicsdb_reader_GenomicsDBQueryStream_jniGenomicsDBInit(&env, nullptr, &l, &q, &c, start, end, 0, 1048576, 1048576, is_bcf ? 1 : 0, 0, 0, 1);
+  const jlong h = Java_com_intel_genomicsdb_reader_GenomicsDBQueryStream_jniGenomicsDBInit(&env, nullptr, &l, &q, &c, start, end, 0, 1048576, 1048576, is_bcf ? 1 : 0, 0,
+                                                                                           use_missing_values_only_not_vector_end ? 1 : 0, keep_idx_fields_in_bcf_header ? 1 : 0);
   if (env.exception_pending || !h) return fail("Init: " + env.exception_text);
   if (Java_com_intel_genomicsdb_reader_GenomicsDBQueryStream_jniGenomicsDBGetNumBytesAvailable(&env, nullptr, h) != 1048576) return fail("GetNumBytesAvailable");
   std::vector<unsigned char> all;
@@ -79,5 +82,10 @@ extern "C" int jni_harness_read_stream(const char* loader_json, const char* quer
   memcpy(*out, all.data(), all.size());
   *nbytes = all.size();
   return 0;
+}
+// the stream with the library's defaults for the last two flags (vector_end padding, IDX keys kept)
+extern "C" int jni_harness_read_stream(const char* loader_json, const char* query_json, const char* chr, int start, int end, int is_bcf, int array_len, int use_read_next_byte_first,
+                                       unsigned char** out, unsigned long long* nbytes, char* err, unsigned long long err_cap) {
+  return jni_harness_read_stream_flags(loader_json, query_json, chr, start, end, is_bcf, 0, 1, array_len, use_read_next_byte_first, out, nbytes, err, err_cap);
 }
 extern "C" void jni_harness_free(void* p) { free(p); }

@@ -1009,31 +1009,37 @@ def test_bcf_stream_decodes_to_the_golden_text(gdb, case, monkeypatch):
 
 
 def test_bcf_htsjdk_flag_uses_missing_values_only(gdb):
-    """use_missing_values_only_not_vector_end (the JNI flag for htsjdk, which has no vector-end values): no vector-end code
-    anywhere in the FORMAT blocks, absent GT = no-call alleles; the records still decode"""
-    import bcf2text
-    case = [c for c in CASES if c[0] == "t0_haploid_triploid_1_2_3_triploid_deletion_vcf"][0]
-    name, callsets, vid, ov, golden, mode = case
-    cells = helpers.cells_for(callsets, vid)
-    q, pb = helpers.query_json(callsets, vid, ov, mode)
-    s = gdb.GenomicsDBQueryStream(query_json=q, cells=cells, buffer_capacity=1 << 20, is_bcf=True, use_missing_values_only_not_vector_end=True)
-    data = s.read()
-    s.close()
-    hdr, recs = bcf2text.parse_stream(data)
-    assert recs
-    text = helpers.bcf_stream_to_text(data).decode()
-    body = [l for l in text.split("\n") if l and not l.startswith("#")]
-    want = [l for l in helpers.golden_text(golden).decode().split("\n") if l and not l.startswith("#")]
-    assert len(body) == len(want)
-    for got_line, want_line in zip(body, want):
-        g, w = got_line.split("\t"), want_line.split("\t")
-        assert g[:9] == w[:9]
-        for gs, ws in zip(g[9:], w[9:]):       # same values; shorter vectors are padded with '.' instead of being cut
-            for gf, wf in zip(gs.split(":"), ws.split(":")):
-                gf = gf.replace("-65", ".")      # a GT padded with the int8 MISSING code, as htslib's bcf_format_gt prints it ((-128 >> 1) - 1)
-                gv, wv = gf.replace("/", ",").replace("|", ",").split(","), wf.replace("/", ",").replace("|", ",").split(",")
-                assert gv[:len(wv)] == wv or wv == ["."], (gf, wf)
-                assert all(x == "." for x in gv[len(wv):]), (gf, wf, got_line[:120])
+    """use_missing_values_only_not_vector_end (the JNI flag for htsjdk, which has no vector-end values) against the exact rule of the
+    reference's collect_and_extend_fields (variant_field_handler.cc:846-866; htsjdk_text.expected_flagged) applied to the DEFAULT
+    stream's records: the shared block byte for byte, the FORMAT fields with the same keys, types and lengths, every element as a raw
+    integer / float bit pattern - padding is missing, an absent GT one no-call allele then missing, an absent string NULs.
+    (The synthetic shapes go through the same rule in tests/test_gpu_java_goldens.py.)"""
+    import htsjdk_text
+    vends = absent_gt = 0
+    for case_name in ("t0_haploid_triploid_1_2_3_triploid_deletion_vcf", "t0_1_2_vcf_at_0", "t6_7_8_vcf_at_0"):
+        name, callsets, vid, ov, golden, mode = [c for c in CASES if c[0] == case_name][0]
+        cells = helpers.cells_for(callsets, vid)
+        q, pb = helpers.query_json(callsets, vid, ov, mode)
+        streams = []
+        for flag in (False, True):
+            s = gdb.GenomicsDBQueryStream(query_json=q, cells=cells, buffer_capacity=1 << 20, is_bcf=True, use_missing_values_only_not_vector_end=flag)
+            streams.append(htsjdk_text.parse_stream(s.read()))
+            s.close()
+        (hdr, default), (hdr_f, flagged) = streams
+        assert hdr_f.text == hdr.text
+        assert default and len(flagged) == len(default)
+        for d, f in zip(default, flagged):
+            d, f = htsjdk_text.decode_record(hdr, d), htsjdk_text.decode_record(hdr, f)
+            assert htsjdk_text.flag_rule_mismatch(d, f) is None, case_name
+            for fname, t, n, per in d.fmt:
+                if t != htsjdk_text.BT_CHAR:
+                    vend = htsjdk_text._missing_vend(t)[1]
+                    vends += sum(v.count(vend) for v in per)
+                    absent_gt += sum(1 for v in per if fname == "GT" and v[0] == vend)
+            for fname, t, n, per in f.fmt:       # and no vector_end is left anywhere
+                if t != htsjdk_text.BT_CHAR:
+                    assert not any(htsjdk_text._missing_vend(t)[1] in v for v in per), (case_name, d.pos, fname)
+    assert vends > 0 and absent_gt > 0      # the default streams had something for the flag to change
 
 
 def test_bcf_synthetic_widths_and_text_agree(gdb, tmp_path):
