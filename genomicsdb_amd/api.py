@@ -361,7 +361,7 @@ INFLATE_MODES = {"auto": 0, "host": 1, "device": 2}
 
 
 def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_deletions_as_intervals=True, column_begin=0, column_end=2**63 - 2,
-                 device=None, text_budget_bytes=0, stats=None, inflate="auto", streams=None):
+                 device=None, text_budget_bytes=0, stats=None, inflate="auto", streams=None, lb_callset_row_idx=0, ub_callset_row_idx=2**63 - 2):
     """(g)VCFs of a callset mapping -> begin-cells (bytes, reference binary cell layout, column-major) of one column partition:
     the conversion step of the reference's vcf2tiledb (vcf2binary.cc:991-1196).
     device=None: host code, no device needed.  device=<int>: the conversion runs on that GPU (kernels/gdb_import.hip) and gives
@@ -374,7 +374,11 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
     host importer refuses a BCF2 file by name.  streams (device path only): {name: bytes} - a callset whose "filename" equals a name is
     read from those bytes (VCF text or BCF2, plain or gzip) instead of a file; a name that no callset uses is an error.
     CSV cell files (device path only): a "filename" that the callset mapping also lists under "sorted_csv_files" / "unsorted_csv_files"
-    is read as the reference loader's CSV input, one line = one cell (csrc/core/gdb_import_csv.hpp); from a file or from streams=."""
+    is read as the reference loader's CSV input, one line = one cell (csrc/core/gdb_import_csv.hpp); from a file or from streams=.
+    lb_callset_row_idx / ub_callset_row_idx (the loader JSON keys of an incremental import, host and device path): only the callsets
+    whose row_idx lies inside are converted - clamped as the reference does (negative -> 0, swapped when reversed, capped at the
+    mapping's largest row).  A file or stream without such a callset is not opened and not counted in stats["num_files"] (which the
+    host path fills too); merge_cells puts the batch next to the cells an array already holds."""
     if inflate not in INFLATE_MODES:
         raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
     if streams is not None and device is None:
@@ -384,8 +388,12 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
     n = ctypes.c_uint64()
     nc = ctypes.c_int64()
     if device is None:
-        rc = L.gdbamd_import_cells(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), 1 if treat_deletions_as_intervals else 0,
-                                   column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc))
+        nf = ctypes.c_int64()
+        rc = L.gdbamd_import_cells_rows(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), 1 if treat_deletions_as_intervals else 0,
+                                        column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc), int(lb_callset_row_idx), int(ub_callset_row_idx),
+                                        ctypes.byref(nf))
+        if rc == 0 and stats is not None:
+            stats.update({"num_files": nf.value, "num_cells": nc.value, "num_bytes": n.value})
     else:
         st = (ctypes.c_double * len(IMPORT_STAT_NAMES))()
         items = [(os.fsencode(k), bytes(v)) for k, v in (streams or {}).items()]
@@ -393,14 +401,46 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
         names = (ctypes.c_char_p * max(ns, 1))(*[k for k, _ in items])
         data = (ctypes.c_void_p * max(ns, 1))(*[ctypes.cast(ctypes.c_char_p(v), ctypes.c_void_p) for _, v in items])      # (items keeps the bytes alive)
         sizes = (ctypes.c_uint64 * max(ns, 1))(*[len(v) for _, v in items])
-        rc = L.gdbamd_import_cells_device_streams(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
+        rc = L.gdbamd_import_cells_device_rows(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""),
                                                   1 if treat_deletions_as_intervals else 0, column_begin, column_end, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc),
-                                                  int(device), int(text_budget_bytes), INFLATE_MODES[inflate], st, len(IMPORT_STAT_NAMES), ns, names, data, sizes)
+                                                  int(device), int(text_budget_bytes), INFLATE_MODES[inflate], st, len(IMPORT_STAT_NAMES), ns, names, data, sizes,
+                                               int(lb_callset_row_idx), int(ub_callset_row_idx))
         if rc == 0 and stats is not None:
             stats.update({k: (float(v) if k[:2] in ("ms", "s_") else int(v)) for k, v in zip(IMPORT_STAT_NAMES, st)})
     _check(rc == 0, "import_cells")
     try:
         return ctypes.string_at(p.value, n.value), nc.value
+    finally:
+        L.gdbamd_free(p)
+
+
+MERGE_STAT_NAMES = ("num_streams", "cells_in", "cells_out", "bytes_out", "tile", "ms_keys", "ms_rank", "ms_scan", "ms_gather", "s_h2d", "s_d2h", "s_total")
+
+
+def merge_cells(streams, device=0, stats=None):
+    """k >= 1 streams of begin-cells (bytes; each in column-major (column, row) order, as import_cells or a cells.bin gives them) ->
+    (bytes, ncells) of the one stream in that order, merged on GPU `device` (kernels/gdb_merge.hip): how the batch of an incremental
+    import joins the cells an array already holds.  Only each cell's 24-byte header is read.  Raises, with nothing returned, for a
+    size chain that runs past its stream's end, a stream that is not sorted, a negative row and a row that two streams share.
+    `stats`, a dict, receives MERGE_STAT_NAMES ("tile": output cells per workgroup of the rank kernel)."""
+    L = _lib.lib()
+    items = [bytes(s) for s in streams]
+    k = len(items)
+    if k == 0:
+        raise ValueError("merge_cells: at least one stream")
+    data = (ctypes.c_void_p * k)(*[ctypes.cast(ctypes.c_char_p(v), ctypes.c_void_p) for v in items])      # (items keeps the bytes alive)
+    sizes = (ctypes.c_uint64 * k)(*[len(v) for v in items])
+    p = ctypes.c_void_p()
+    n = ctypes.c_uint64()
+    nc = ctypes.c_int64()
+    st = (ctypes.c_double * len(MERGE_STAT_NAMES))()
+    rc = L.gdbamd_merge_cells(k, data, sizes, ctypes.byref(p), ctypes.byref(n), ctypes.byref(nc), int(device), st, len(MERGE_STAT_NAMES))
+    _check(rc == 0, "merge_cells")
+    if stats is not None:
+        stats.update({name: (float(v) if name[:2] in ("ms", "s_") else int(v)) for name, v in zip(MERGE_STAT_NAMES, st)})
+    try:
+        # (ctypes.string_at takes a C int: a merged array of 2 GiB and more goes the long way)
+        return (ctypes.string_at(p.value, n.value) if n.value < (1 << 31) else bytes((ctypes.c_ubyte * n.value).from_address(p.value))), nc.value
     finally:
         L.gdbamd_free(p)
 

@@ -20,6 +20,7 @@ SOURCES = [
     "kernels/gdb_bgzf.hip",
     "kernels/gdb_import.hip",
     "kernels/gdb_inflate.hip",
+    "kernels/gdb_merge.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -137,6 +138,14 @@ def build_hostsim_import_csv():
     d = os.path.join(ROOT, "tests", "hostsim_import_csv")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "libhostsim_import_csv.so"), os.path.join(d, "hostsim_import_csv_main")
+
+
+def build_hostsim_merge():
+    """CPU harness around the bodies of the cell-stream merge (core/gdb_merge.hpp) and the same source as a stand-alone program
+    built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_merge")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_merge.so"), os.path.join(d, "hostsim_merge_main")
 
 
 def build_hostsim_inflate():

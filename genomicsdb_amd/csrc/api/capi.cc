@@ -429,6 +429,12 @@ int gdbamd_column_partition(const char* loader_json_text, int rank, int64_t* beg
 
 int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
                         int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells) {
+  return gdbamd_import_cells_rows(vid_mapping_file, callset_mapping_file, file_root, treat_deletions_as_intervals, column_begin, column_end, cells, nbytes, ncells, 0,
+                                  INT64_MAX - 1, nullptr);
+}
+int gdbamd_import_cells_rows(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                             int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int64_t lb_callset_row_idx,
+                             int64_t ub_callset_row_idx, int64_t* nfiles) {
   try {
     if (!vid_mapping_file || !callset_mapping_file || !cells || !nbytes) throw GenomicsDBConfigException("gdbamd_import_cells: null argument");
     VidMapper vid;
@@ -439,6 +445,8 @@ int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mappin
     opt.column_begin = column_begin;
     opt.column_end = column_end;
     if (file_root) opt.file_root = file_root;
+    opt.row_begin = lb_callset_row_idx;
+    opt.row_end = ub_callset_row_idx;
     ImportStats st;
     const std::vector<uint8_t> out = import_callsets_to_cells(vid, opt, &st);
     *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
@@ -446,6 +454,7 @@ int gdbamd_import_cells(const char* vid_mapping_file, const char* callset_mappin
     if (!out.empty()) memcpy(*cells, out.data(), out.size());
     *nbytes = out.size();
     if (ncells) *ncells = st.num_cells;
+    if (nfiles) *nfiles = st.num_files;
     g_last_error.clear();
     return 0;
   } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
@@ -466,6 +475,13 @@ int gdbamd_import_cells_device_streams(const char* vid_mapping_file, const char*
                                        int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device,
                                        uint64_t text_budget_bytes, int inflate_mode, double* stats, int nstats, int nstreams, const char* const* names,
                                        const void* const* data, const uint64_t* stream_nbytes) {
+  return gdbamd_import_cells_device_rows(vid_mapping_file, callset_mapping_file, file_root, treat_deletions_as_intervals, column_begin, column_end, cells, nbytes, ncells,
+                                         device, text_budget_bytes, inflate_mode, stats, nstats, nstreams, names, data, stream_nbytes, 0, INT64_MAX - 1);
+}
+int gdbamd_import_cells_device_rows(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                                    int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device,
+                                    uint64_t text_budget_bytes, int inflate_mode, double* stats, int nstats, int nstreams, const char* const* names,
+                                    const void* const* data, const uint64_t* stream_nbytes, int64_t lb_callset_row_idx, int64_t ub_callset_row_idx) {
   try {
     if (!vid_mapping_file || !callset_mapping_file || !cells || !nbytes) throw GenomicsDBConfigException("gdbamd_import_cells_device: null argument");
     if (nstreams < 0 || (nstreams > 0 && (!names || !data || !stream_nbytes))) throw GenomicsDBConfigException("gdbamd_import_cells_device_streams: null stream arrays");
@@ -484,6 +500,8 @@ int gdbamd_import_cells_device_streams(const char* vid_mapping_file, const char*
     opt.column_begin = column_begin;
     opt.column_end = column_end;
     if (file_root) opt.file_root = file_root;
+    opt.row_begin = lb_callset_row_idx;
+    opt.row_end = ub_callset_row_idx;
     ImportStats st;
     const std::vector<uint8_t> out = import_callsets_to_cells_device(vid, opt, device, text_budget_bytes, &st, inflate_mode, streams);
     *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
@@ -497,6 +515,28 @@ int gdbamd_import_cells_device_streams(const char* vid_mapping_file, const char*
                                                     st.ms_sort_gather, st.s_read, st.s_h2d, st.s_deferred, st.s_d2h, st.s_total,
                                                     (double)st.compressed_bytes, (double)st.num_device_members, (double)st.num_host_inflated_files, st.ms_inflate, (double)st.bytes_h2d};
       memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_IMPORT_NUM_STATS_EX));
+    }
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nbytes, uint8_t** cells, uint64_t* out_nbytes, int64_t* ncells, int device, double* stats,
+                       int nstats) {
+  try {
+    if (nstreams <= 0 || !data || !nbytes || !cells || !out_nbytes) throw GenomicsDBConfigException("gdbamd_merge_cells: null argument or no stream");
+    std::vector<CellStream> streams((size_t)nstreams);
+    for (int i = 0; i < nstreams; ++i) { streams[(size_t)i].data = data[i]; streams[(size_t)i].nbytes = nbytes[i]; }
+    MergeStats st;
+    const std::vector<uint8_t> out = merge_cell_streams_device(streams, device, &st);
+    *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
+    if (!*cells) throw GenomicsDBConfigException("out of memory");
+    if (!out.empty()) memcpy(*cells, out.data(), out.size());
+    *out_nbytes = out.size();
+    if (ncells) *ncells = st.cells_out;
+    if (stats && nstats > 0) {
+      const double v[GDBAMD_MERGE_NUM_STATS] = {(double)st.num_streams, (double)st.cells_in, (double)st.cells_out, (double)st.bytes_out, (double)st.tile,
+                                                st.ms_keys, st.ms_rank, st.ms_scan, st.ms_gather, st.s_h2d, st.s_d2h, st.s_total};
+      memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_MERGE_NUM_STATS));
     }
     g_last_error.clear();
     return 0;

@@ -88,12 +88,13 @@ inline ImportTablesHost build_import_tables(const VidMapper& vid) {
 }
 
 struct ImportFile { std::string name, path; std::vector<const CallSetInfo*> callsets; GdbFileType type = GDB_FILE_VCF; };
-// callsets grouped by file, in mapping order
+// callsets grouped by file, in mapping order; only the callsets inside opt's row bounds, and only the files that have one
 inline std::vector<ImportFile> import_files(const VidMapper& vid, const ImportOptions& opt) {
   std::vector<ImportFile> files;
   std::unordered_map<std::string, size_t> at;
   for (const CallSetInfo& cs : vid.get_callsets()) {
     if (cs.m_filename.empty()) throw VCF2BinaryException("callset " + cs.m_name + " has no \"filename\"");
+    if (!row_in_bounds(opt, cs.m_row_idx)) continue;
     if (!at.count(cs.m_filename)) {
       at[cs.m_filename] = files.size();
       ImportFile f;

@@ -69,6 +69,13 @@ void GenomicsDBImportConfig::read_from_json(const mini_json::Value& j, int rank)
   if (j.HasMember("reference_genome")) m_reference_genome = pick_rank(j["reference_genome"], rank).GetString();
   m_treat_deletions_as_intervals = j.HasMember("treat_deletions_as_intervals") && j["treat_deletions_as_intervals"].GetBool();
   m_produce_combined_vcf = j.HasMember("produce_combined_vcf") && j["produce_combined_vcf"].GetBool();
+  if (j.HasMember("lb_callset_row_idx")) m_lb_callset_row_idx = j["lb_callset_row_idx"].GetInt64();
+  if (j.HasMember("ub_callset_row_idx")) m_ub_callset_row_idx = j["ub_callset_row_idx"].GetInt64();
+  if (m_lb_callset_row_idx < 0) m_lb_callset_row_idx = 0;
+  if (m_ub_callset_row_idx < 0) m_ub_callset_row_idx = 0;
+  if (m_ub_callset_row_idx < m_lb_callset_row_idx) std::swap(m_lb_callset_row_idx, m_ub_callset_row_idx);
+  m_has_delete_and_create_tiledb_array = j.HasMember("delete_and_create_tiledb_array");
+  m_delete_and_create_tiledb_array = m_has_delete_and_create_tiledb_array && j["delete_and_create_tiledb_array"].GetBool();
   if (j.HasMember("workspace")) { const auto& w = j["workspace"]; if (w.IsArray()) for (size_t i = 0; i < w.Size(); ++i) m_workspaces.push_back(w[i].GetString()); else m_workspaces.push_back(w.GetString()); }
   const char* ak = j.HasMember("array") ? "array" : (j.HasMember("array_name") ? "array_name" : nullptr);
   if (ak) { const auto& a = j[ak]; if (a.IsArray()) for (size_t i = 0; i < a.Size(); ++i) m_array_names.push_back(a[i].GetString()); else m_array_names.push_back(a.GetString()); }

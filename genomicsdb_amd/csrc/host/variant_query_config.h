@@ -37,6 +37,11 @@ class GenomicsDBImportConfig {
   std::vector<ColumnRange> m_sorted_column_partitions, m_column_partitions;
   std::vector<std::string> m_workspaces, m_array_names;
   bool m_treat_deletions_as_intervals = false, m_produce_combined_vcf = false;
+  // the rows of this batch (json_config.cc:747-753), negative -> 0 and swapped when reversed as fix_callset_row_idx_bounds does
+  // (genomicsdb_config_base.cc:167-180); the cap at the mapping's largest row is the importer's, which has the mapping
+  int64_t m_lb_callset_row_idx = 0, m_ub_callset_row_idx = INT64_MAX - 1;
+  // "delete_and_create_tiledb_array": vcf2tiledb merges into an existing array only when the key is there and false
+  bool m_delete_and_create_tiledb_array = false, m_has_delete_and_create_tiledb_array = false;
   bool m_loaded = false;
 };
 

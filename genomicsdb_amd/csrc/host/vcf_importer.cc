@@ -222,8 +222,9 @@ float import_csv_parse_float(const char* p, size_t n, const std::string& what) {
   return v;
 }
 
-std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const ImportOptions& opt, ImportStats* stats) {
+std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const ImportOptions& options, ImportStats* stats) {
   if (!vid.is_initialized() || !vid.is_callset_mapping_initialized()) throw VCF2BinaryException("vid and callset mappings are needed");
+  const ImportOptions opt = with_clamped_row_bounds(options, vid);
   // attribute order of the schema (same walk as VidMapper::schema_attribute_names)
   const bool has_id = vid.get_field_info("ID") != nullptr;
   std::vector<Attr> info_attrs, fmt_attrs;
@@ -252,6 +253,7 @@ std::vector<uint8_t> import_callsets_to_cells(const VidMapper& vid, const Import
   std::unordered_map<std::string, std::vector<const CallSetInfo*>> by_file;
   for (const CallSetInfo& cs : vid.get_callsets()) {
     if (cs.m_filename.empty()) throw VCF2BinaryException("callset " + cs.m_name + " has no \"filename\"");
+    if (!row_in_bounds(opt, cs.m_row_idx)) continue;      // not of this batch: a file without a callset in bounds is not opened
     if (!by_file.count(cs.m_filename)) files.push_back(cs.m_filename);
     by_file[cs.m_filename].push_back(&cs);
   }

@@ -35,7 +35,26 @@ struct ImportOptions {
   bool treat_deletions_as_intervals = false;       // loader JSON key of the same name
   int64_t column_begin = 0, column_end = INT64_MAX - 1;   // column partition: cells that begin inside are kept
   std::string file_root;                           // prefix of relative "filename" entries of the callset mapping
+  // loader JSON "lb_callset_row_idx" / "ub_callset_row_idx": only callsets whose row lies inside are converted (an incremental
+  // import); a file without such a callset is not opened.  Clamped by clamp_row_bounds before use
+  int64_t row_begin = 0, row_end = INT64_MAX - 1;
 };
+// GenomicsDBImportConfig::fix_callset_row_idx_bounds of the reference (genomicsdb_config_base.cc:167-180): negative -> 0, swapped when
+// reversed, the upper bound capped at the mapping's largest row (max_row < 0: not known, no cap)
+inline void clamp_row_bounds(int64_t* lb, int64_t* ub, int64_t max_row) {
+  if (*lb < 0) *lb = 0;
+  if (*ub < 0) *ub = 0;
+  if (*ub < *lb) { const int64_t t = *lb; *lb = *ub; *ub = t; }
+  if (max_row >= 0 && *ub > max_row) *ub = max_row;
+}
+inline ImportOptions with_clamped_row_bounds(const ImportOptions& opt, const VidMapper& vid) {
+  ImportOptions o = opt;
+  int64_t max_row = -1;
+  for (const CallSetInfo& cs : vid.get_callsets()) if (cs.m_row_idx > max_row) max_row = cs.m_row_idx;
+  clamp_row_bounds(&o.row_begin, &o.row_end, max_row);
+  return o;
+}
+inline bool row_in_bounds(const ImportOptions& opt, int64_t row) { return row >= opt.row_begin && row <= opt.row_end; }
 struct ImportStats {
   int64_t num_files = 0, num_records = 0, num_cells = 0, num_spanning_cells = 0; uint64_t num_bytes = 0;   // num_spanning_cells: intervals replayed at the partition begin
   // device path only
@@ -67,6 +86,22 @@ struct ImportStream { std::string name; const void* data = nullptr; uint64_t nby
 std::vector<uint8_t> import_callsets_to_cells_device(const VidMapper& vid, const ImportOptions& opt, int device, uint64_t text_budget_bytes,
                                                      ImportStats* stats = nullptr, int inflate_mode = 0,
                                                      const std::vector<ImportStream>& streams = std::vector<ImportStream>());
+
+// Incremental import: k >= 1 streams of begin-cells in host memory, each sorted by (column, row) as an importer or a cells.bin gives
+// them, become one stream in that order on GPU `device` (kernels/gdb_merge.hip; the reference's "new fragment, then
+// consolidate_tiledb_array").  Schema-agnostic: only the 24-byte header of a cell is read, payloads move as opaque bytes.  Refused
+// (VCF2BinaryException, nothing returned): a size chain that runs past its stream's end (stream, byte offset), a stream that is not
+// sorted (stream, cell index), a negative row, and a row that two streams share (the smallest one) - the batches of an incremental
+// import have disjoint rows, so there are no key ties across streams; equal keys inside one stream keep their order.  Inputs, keys and
+// the result must fit in the device's free memory together (refused with the sizes otherwise).  No device: GenomicsDBDeviceException.
+struct CellStream { const void* data = nullptr; uint64_t nbytes = 0; };
+struct MergeStats {
+  int64_t num_streams = 0, cells_in = 0, cells_out = 0; uint64_t bytes_out = 0;
+  int64_t tile = 0;                                        // output cells per workgroup of the rank kernel
+  float ms_keys = 0, ms_rank = 0, ms_scan = 0, ms_gather = 0;   // HIP-event time: keys + checks, merge-path rank rounds, size scatter + scan, gather
+  double s_h2d = 0, s_d2h = 0, s_total = 0;                // wall clock
+};
+std::vector<uint8_t> merge_cell_streams_device(const std::vector<CellStream>& streams, int device, MergeStats* stats = nullptr);
 
 // the importer's number parsers (strtoll / strtod over the whole token, VCF2BinaryException otherwise): the device path runs
 // them on the tokens it deferred

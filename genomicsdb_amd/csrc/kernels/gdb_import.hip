@@ -369,6 +369,7 @@ struct DeviceImporter::Impl {
   uint64_t budget = 0;
   ImportTablesHost H;
   std::vector<ImportFile> files;
+  std::vector<std::string> skipped_files;      // "filename"s whose callsets all lie outside the row bounds: never opened
   ImportStats st;
   hipStream_t stream = nullptr;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -444,14 +445,19 @@ DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOpt
     if (inflate_mode < kInflateAuto || inflate_mode > kInflateDevice) throw VCF2BinaryException("inflate mode " + std::to_string(inflate_mode) + ": 0 (auto), 1 (host) or 2 (device)");
     m_->inflate_mode = inflate_mode;
     m_->device = device;
-    m_->opt = opt;
+    m_->opt = with_clamped_row_bounds(opt, vid);
     m_->budget = text_budget_bytes ? text_budget_bytes : kDefaultTextBudget;
     m_->budget = std::min<uint64_t>(m_->budget, (uint64_t)1 << 30);
     if (const char* e = getenv("GDBAMD_IMPORT_STAGE_LDS")) m_->stage_in_lds = atoi(e) != 0;
     // the A/B of profiles/device_inflate.md: one thread per BGZF member instead of one wavefront (9.6 x slower; kept for that comparison)
     if (const char* e = getenv("GDBAMD_INFLATE_KERNEL")) m_->inflater.set_kernel(std::string(e) == "thread" ? BgzfDeviceInflater::kThreadPerMember : BgzfDeviceInflater::kWavePerMember);
     m_->H = build_import_tables(vid);                 // the refusals: before the device is touched
-    m_->files = import_files(vid, opt);
+    m_->files = import_files(vid, m_->opt);
+    for (const CallSetInfo& cs : vid.get_callsets()) {
+      bool used = false;
+      for (const ImportFile& f : m_->files) used = used || f.name == cs.m_filename;
+      if (!used) m_->skipped_files.push_back(cs.m_filename);
+    }
     refuse_for_csv(vid, m_->H, m_->files);
     Impl& M = *m_;
     if (opt.column_begin > 0) {
@@ -499,6 +505,7 @@ void DeviceImporter::import_all(const std::vector<ImportStream>& streams) {
   for (const ImportStream& s : streams) {
     bool used = false;
     for (const ImportFile& f : m_->files) used = used || f.name == s.name;
+    for (const std::string& name : m_->skipped_files) used = used || name == s.name;      // (of another batch: left alone)
     if (!used) throw VCF2BinaryException("stream " + s.name + " is not a \"filename\" of the callset mapping");
   }
   for (const ImportFile& f : m_->files) {

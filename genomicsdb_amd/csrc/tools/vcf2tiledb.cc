@@ -9,6 +9,11 @@
 // same cells; the default is the host importer.  On the device, bgzip'ed input (BGZF) is inflated there too and crosses the link
 // compressed; --inflate-on-host keeps zlib on the host for every file.  BCF2 files (.bcf, sniffed by content) are read with
 // --import-on-device only; without it the tool names the file and exits with an error.
+// Incremental import: "lb_callset_row_idx" / "ub_callset_row_idx" of the loader JSON choose the callsets of this batch, and with
+//   "delete_and_create_tiledb_array": false  (written out; the reference's default)
+// a batch is MERGED into an existing <workspace>/<array>/cells.bin on the rank's GPU (kernels/gdb_merge.hip), the result written to a
+// temporary name in the same directory and renamed over cells.bin.  With the key absent or true the array file is overwritten.
+// "produce_combined_vcf" in the same run combines the cells of the batch only, like the reference's in-line operator.
 // The --split-files modes of the reference tool are not implemented (exit with an error).
 #include <getopt.h>
 #include <sys/stat.h>
@@ -74,6 +79,8 @@ int main(int argc, char** argv) {
     opt.treat_deletions_as_intervals = loader.m_treat_deletions_as_intervals;
     opt.column_begin = part.first;
     opt.column_end = part.second;
+    opt.row_begin = loader.m_lb_callset_row_idx;
+    opt.row_end = loader.m_ub_callset_row_idx;
     ImportStats st;
     int device = 0;
     if (const char* e = getenv("GDBAMD_DEVICE")) device = atoi(e); else if (const char* e2 = getenv("LOCAL_RANK")) device = atoi(e2);
@@ -88,14 +95,43 @@ int main(int argc, char** argv) {
     if (produce_array) {
       const std::string dir = loader.get_workspace(rank) + "/" + loader.get_array_name(rank);
       mkdir_p(dir);
-      FILE* f = fopen((dir + "/cells.bin").c_str(), "wb");
-      if (!f) throw GenomicsDBConfigException("cannot write " + dir + "/cells.bin");
-      if (!cells.empty() && fwrite(cells.data(), 1, cells.size(), f) != cells.size()) { fclose(f); throw GenomicsDBConfigException("short write to " + dir + "/cells.bin"); }
-      fclose(f);
+      const std::string array_file = dir + "/cells.bin";
+      struct stat have;
+      const bool merge = loader.m_has_delete_and_create_tiledb_array && !loader.m_delete_and_create_tiledb_array && ::stat(array_file.c_str(), &have) == 0;
+      std::vector<uint8_t> merged;
+      if (merge) {      // the batch joins the cells the array holds: on the device, or not at all
+        const auto tm = std::chrono::steady_clock::now();
+        std::vector<uint8_t> old((size_t)have.st_size);
+        FILE* in = fopen(array_file.c_str(), "rb");
+        if (!in) throw GenomicsDBConfigException("cannot read " + array_file);
+        const size_t got = old.empty() ? 0 : fread(old.data(), 1, old.size(), in);
+        fclose(in);
+        if (got != old.size()) throw GenomicsDBConfigException("short read from " + array_file);
+        MergeStats ms;
+        std::vector<CellStream> streams(2);
+        streams[0].data = old.data(); streams[0].nbytes = old.size();
+        streams[1].data = cells.data(); streams[1].nbytes = cells.size();
+        merged = merge_cell_streams_device(streams, device, &ms);
+        std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",merge_tiledb_array,Wall-clock time(s)," << std::chrono::duration<double>(std::chrono::steady_clock::now() - tm).count()
+                  << ",streams," << ms.num_streams << ",cells_in," << ms.cells_in << ",cells_out," << ms.cells_out << ",bytes_out," << ms.bytes_out << ",tile," << ms.tile
+                  << ",keys_ms," << ms.ms_keys << ",rank_ms," << ms.ms_rank << ",scan_ms," << ms.ms_scan << ",gather_ms," << ms.ms_gather << ",h2d_s," << ms.s_h2d
+                  << ",d2h_s," << ms.s_d2h << ",merge_s," << ms.s_total << "\n";
+      }
+      const std::vector<uint8_t>& array_cells = merge ? merged : cells;
+      const std::string write_to = merge ? array_file + ".merge.tmp" : array_file;
+      FILE* f = fopen(write_to.c_str(), "wb");
+      if (!f) throw GenomicsDBConfigException("cannot write " + write_to);
+      if (!array_cells.empty() && fwrite(array_cells.data(), 1, array_cells.size(), f) != array_cells.size()) {
+        fclose(f);
+        if (merge) remove(write_to.c_str());
+        throw GenomicsDBConfigException("short write to " + write_to);
+      }
+      if (fclose(f) != 0) throw GenomicsDBConfigException("cannot write " + write_to);
+      if (merge && rename(write_to.c_str(), array_file.c_str()) != 0) { remove(write_to.c_str()); throw GenomicsDBConfigException("cannot rename " + write_to + " to " + array_file); }
       remove((dir + "/fragment.gdbamd").c_str());   // a columnar copy of older cells must not shadow the new array
       // "compress_tiledb_array" (the reference's loader gzips the attribute tiles of the array it writes): the columnar fragment file with
       // its data sections as DEFLATE tiles goes next to cells.bin; queries read it window by window and inflate the tiles on the device
-      if (doc.HasMember("compress_tiledb_array") && doc["compress_tiledb_array"].GetBool() && !cells.empty()) {
+      if (doc.HasMember("compress_tiledb_array") && doc["compress_tiledb_array"].GetBool() && !array_cells.empty()) {
         const auto tc = std::chrono::steady_clock::now();
         const size_t close_at = loader_text.rfind('}');
         if (close_at == std::string::npos) throw GenomicsDBConfigException("loader JSON is not an object");
@@ -103,12 +139,12 @@ int main(int argc, char** argv) {
                                      loader_text.substr(close_at);
         try {
           CombineEngine eng(mini_json::parse(all_text), 0, nullptr, rank, "", false);
-          eng.stage_cells(cells.data(), cells.size());
+          eng.stage_cells(array_cells.data(), array_cells.size());
           eng.save_fragment(dir + "/fragment.gdbamd", true);
           struct stat fs;
           const long long zbytes = ::stat((dir + "/fragment.gdbamd").c_str(), &fs) == 0 ? (long long)fs.st_size : -1;
           std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",compress_tiledb_array,Wall-clock time(s)," << std::chrono::duration<double>(std::chrono::steady_clock::now() - tc).count()
-                    << ",cells_bytes," << cells.size() << ",fragment_bytes," << zbytes << "\n";
+                    << ",cells_bytes," << array_cells.size() << ",fragment_bytes," << zbytes << "\n";
         } catch (const GenomicsDBDeviceException& e) {
           // (the columnar file is built from columns staged in HBM: without a device the array stays as cells.bin, which every reader accepts)
           std::cerr << "vcf2tiledb: compress_tiledb_array skipped: " << e.what() << "\n";

@@ -296,6 +296,29 @@ int gdbamd_import_cells_device_streams(const char* vid_mapping_file, const char*
                                        int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device,
                                        uint64_t text_budget_bytes, int inflate_mode, double* stats, int nstats, int nstreams, const char* const* names,
                                        const void* const* data, const uint64_t* stream_nbytes);
+/* Incremental import (the loader JSON's "lb_callset_row_idx" / "ub_callset_row_idx", src/main/cpp/src/loader/tiledb_loader.cc:107-139): the two imports
+ * above for the callsets whose row_idx lies in [lb, ub] only - clamped as the reference clamps them (negative -> 0, swapped when reversed, ub capped at the
+ * mapping's largest row; genomicsdb_config_base.cc:167-180).  A file or stream without a callset in bounds is not opened and not counted (*nfiles, stats
+ * slot 0); of a multi-sample file only the samples in bounds give cells, and a sum-like INFO value is still divided by the number of samples in the file's
+ * header, so a file split across batches gives the cells of the file imported at once.  lb 0 and ub INT64_MAX - 1 are the calls above. */
+int gdbamd_import_cells_rows(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                             int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int64_t lb_callset_row_idx,
+                             int64_t ub_callset_row_idx, int64_t* nfiles);
+int gdbamd_import_cells_device_rows(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int treat_deletions_as_intervals,
+                                    int64_t column_begin, int64_t column_end, uint8_t** cells, uint64_t* nbytes, int64_t* ncells, int device,
+                                    uint64_t text_budget_bytes, int inflate_mode, double* stats, int nstats, int nstreams, const char* const* names,
+                                    const void* const* data, const uint64_t* stream_nbytes, int64_t lb_callset_row_idx, int64_t ub_callset_row_idx);
+/* The other half of an incremental import: nstreams >= 1 streams of begin-cells in host memory, each in column-major (column, row) order as the imports above
+ * or a cells.bin give them, merged into one stream in that order on GPU `device` (kernels/gdb_merge.hip) - what the reference reaches with a new fragment
+ * and consolidate_tiledb_array.  Only the 24-byte header [row i64][col i64][cell_size u64] of a cell is read; payloads move as opaque bytes.  Errors (-1, no
+ * result): a size chain that runs past its stream's end (stream index and byte offset), a stream that is not sorted (stream and cell index), a negative row,
+ * a row that two streams share (the smallest).  Equal keys inside one stream keep their order.  Streams, keys and result must fit in device memory together.
+ * *cells is malloc'ed: release with gdbamd_free.  stats: NULL or nstats doubles:
+ *   0 streams, 1 cells in, 2 cells out, 3 bytes out, 4 output cells per workgroup of the rank kernel (its tile),
+ *   5..8 HIP-event ms of keys + checks / rank / size scan / gather, 9..11 wall seconds of H2D, D2H, total */
+#define GDBAMD_MERGE_NUM_STATS 12
+int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nbytes, uint8_t** cells, uint64_t* out_nbytes, int64_t* ncells, int device,
+                       double* stats, int nstats);
 void gdbamd_free(void* p);
 
 #ifdef __cplusplus
