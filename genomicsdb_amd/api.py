@@ -414,6 +414,49 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
         L.gdbamd_free(p)
 
 
+SPLIT_STAT_NAMES = ("num_files", "num_record_lines", "num_lines_written", "text_bytes_in", "text_bytes_out", "compressed_bytes_out", "num_batches", "ms_index",
+                    "ms_classify", "ms_scan_gather", "ms_deflate", "s_read", "s_h2d", "s_d2h_write", "s_index_build", "s_total", "ms_inflate")
+
+
+def split_files(vid_mapping_file, callset_mapping_file, partitions, results_directory=None, file_root="", produce=None, device=0, text_budget_bytes=0, stats=None,
+                output_filename=None, extra_files=(), inflate="auto"):
+    """vcf2tiledb --split-files on GPU `device` (kernels/gdb_split.hip): every (g)VCF text file of the callset mapping (plain, gzip or
+    BGZF), then `extra_files`, cut into one BGZF file + .tbi per column partition in one pass per file.  partitions: [(begin, end)]
+    per partition index, as the loader JSON's column_partitions give them with derived ends (column_partition()).  A partition's
+    file holds every '#' line and, verbatim and in file order, every record line whose interval [col, tend] overlaps it (tend from
+    INFO END, else col + len(REF) - 1); a line that spans partitions goes to each.  produce: one partition index, None for all.
+    Outputs: <results_directory or the input's directory>/partition_<p>_<basename>, or what the callset mapping's
+    "split_files_paths" names; output_filename names the output of exactly one input and one partition.
+    -> {(original filename, partition index): output path}.  BCF2 and CSV inputs are refused by name; a line error names file
+    and line and leaves no output of that input.  `stats`, a dict, receives SPLIT_STAT_NAMES."""
+    if inflate not in INFLATE_MODES:
+        raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
+    L = _lib.lib()
+    parts = [(int(b), int(e)) for b, e in partitions]
+    n = len(parts)
+    begins = (ctypes.c_int64 * max(n, 1))(*[b for b, _ in parts])
+    ends = (ctypes.c_int64 * max(n, 1))(*[e for _, e in parts])
+    extra = [os.fsencode(p) for p in extra_files]
+    extra_arr = (ctypes.c_char_p * max(len(extra), 1))(*extra)
+    st = (ctypes.c_double * len(SPLIT_STAT_NAMES))()
+    out = ctypes.c_void_p()
+    rc = L.gdbamd_split_files_device(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), n, begins, ends,
+                                     -1 if produce is None else int(produce), os.fsencode(results_directory or ""), os.fsencode(output_filename or ""), int(device),
+                                     int(text_budget_bytes), INFLATE_MODES[inflate], len(extra), extra_arr, st, len(SPLIT_STAT_NAMES), ctypes.byref(out))
+    _check(rc == 0, "split_files")
+    try:
+        text = ctypes.string_at(out.value).decode()
+    finally:
+        L.gdbamd_free(out)
+    if stats is not None:
+        stats.update({k: (float(v) if k[:2] in ("ms", "s_") else int(v)) for k, v in zip(SPLIT_STAT_NAMES, st)})
+    result = {}
+    for line in text.splitlines():
+        original, p, path = line.split("\t")
+        result[(original, int(p))] = path
+    return result
+
+
 MERGE_STAT_NAMES = ("num_streams", "cells_in", "cells_out", "bytes_out", "tile", "ms_keys", "ms_rank", "ms_scan", "ms_gather", "s_h2d", "s_d2h", "s_total")
 
 

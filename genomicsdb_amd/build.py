@@ -21,6 +21,7 @@ SOURCES = [
     "kernels/gdb_import.hip",
     "kernels/gdb_inflate.hip",
     "kernels/gdb_merge.hip",
+    "kernels/gdb_split.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -146,6 +147,14 @@ def build_hostsim_merge():
     d = os.path.join(ROOT, "tests", "hostsim_merge")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "libhostsim_merge.so"), os.path.join(d, "hostsim_merge_main")
+
+
+def build_hostsim_split():
+    """The bodies of the device splitter (core/gdb_split.hpp) as a stand-alone program built with the address and
+    undefined-behaviour sanitizers (tests only); -> program"""
+    d = os.path.join(ROOT, "tests", "hostsim_split")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "hostsim_split")
 
 
 def build_hostsim_inflate():

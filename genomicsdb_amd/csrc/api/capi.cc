@@ -10,6 +10,7 @@
 #include "genomicsdb_bcf_generator.h"
 #include "../kernels/gdb_bgzf.h"
 #include "../kernels/gdb_inflate.h"
+#include "../kernels/gdb_split.h"
 #include "../host/vcf_importer.h"
 #include "../host/vcf_index.h"
 
@@ -537,6 +538,42 @@ int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nb
       const double v[GDBAMD_MERGE_NUM_STATS] = {(double)st.num_streams, (double)st.cells_in, (double)st.cells_out, (double)st.bytes_out, (double)st.tile,
                                                 st.ms_keys, st.ms_rank, st.ms_scan, st.ms_gather, st.s_h2d, st.s_d2h, st.s_total};
       memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_MERGE_NUM_STATS));
+    }
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
+                              const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
+                              uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs) {
+  try {
+    if (!vid_mapping_file || !callset_mapping_file || npartitions <= 0 || !begins || !ends) throw GenomicsDBConfigException("gdbamd_split_files_device: null argument or no partition");
+    if (nextra < 0 || (nextra > 0 && !extra_paths)) throw GenomicsDBConfigException("gdbamd_split_files_device: null extra_paths");
+    VidMapper vid;
+    vid.parse_vid_json(mini_json::parse_file(vid_mapping_file));
+    vid.parse_callsets_json(mini_json::parse_file(callset_mapping_file));
+    SplitRequest req;
+    for (int i = 0; i < npartitions; ++i) req.partitions.emplace_back(begins[i], ends[i]);
+    if (produce >= 0) req.produce.push_back(produce);
+    if (file_root) req.file_root = file_root;
+    if (results_directory) req.results_directory = results_directory;
+    if (single_output_name) req.single_output = single_output_name;
+    for (int i = 0; i < nextra; ++i) { if (!extra_paths[i]) throw GenomicsDBConfigException("gdbamd_split_files_device: null extra path"); req.extra_paths.push_back(extra_paths[i]); }
+    req.device = device; req.text_budget_bytes = text_budget_bytes; req.inflate_mode = inflate_mode;
+    SplitStats st;
+    const std::vector<SplitOutput> done = split_files_device(vid, req, &st);
+    if (outputs) {
+      std::string text;
+      for (const SplitOutput& o : done) text += o.original + "\t" + std::to_string(o.partition) + "\t" + o.path + "\n";
+      *outputs = (char*)malloc(text.size() + 1);
+      if (!*outputs) throw GenomicsDBConfigException("out of memory");
+      memcpy(*outputs, text.c_str(), text.size() + 1);
+    }
+    if (stats && nstats > 0) {
+      const double v[GDBAMD_SPLIT_NUM_STATS] = {(double)st.num_files, (double)st.num_record_lines, (double)st.num_lines_written, (double)st.text_bytes_in, (double)st.text_bytes_out,
+                                                (double)st.compressed_bytes_out, (double)st.num_batches, st.ms_index, st.ms_classify, st.ms_scan_gather, st.ms_deflate,
+                                                st.s_read, st.s_h2d, st.s_d2h_write, st.s_index_build, st.s_total, st.ms_inflate};
+      memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_SPLIT_NUM_STATS));
     }
     g_last_error.clear();
     return 0;

@@ -6,6 +6,7 @@
 #pragma once
 #include <cerrno>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -200,5 +201,51 @@ inline std::string read_text_file(const std::string& path) {
 }
 
 inline Value parse_file(const std::string& path) { return parse(read_text_file(path)); }
+
+// ---- writing (the JSON files of vcf2tiledb --split-callset-mapping-file): members in their order, two spaces per level
+inline std::string quoted(const std::string& s) {
+  std::string o = "\"";
+  for (const char ch : s) {
+    const unsigned char c = (unsigned char)ch;
+    if (c == '"' || c == '\\') { o.push_back('\\'); o.push_back(ch); }
+    else if (c == '\n') o += "\\n";
+    else if (c == '\t') o += "\\t";
+    else if (c == '\r') o += "\\r";
+    else if (c < 0x20) { char buf[8]; snprintf(buf, sizeof(buf), "\\u%04x", (unsigned)c); o += buf; }
+    else o.push_back(ch);
+  }
+  return o + "\"";
+}
+inline void serialize_to(const Value& v, std::string& o, int depth) {
+  const std::string pad((size_t)depth * 2 + 2, ' '), close((size_t)depth * 2, ' ');
+  switch (v.type) {
+    case Value::Null: o += "null"; break;
+    case Value::Bool: o += v.b ? "true" : "false"; break;
+    case Value::Int: o += std::to_string(v.i); break;
+    case Value::Double: { char buf[40]; snprintf(buf, sizeof(buf), "%.17g", v.d); o += buf; if (!strpbrk(buf, ".eEn")) o += ".0"; break; }
+    case Value::String: o += quoted(v.s); break;
+    case Value::Array:
+      if (v.arr.empty()) { o += "[]"; break; }
+      o += "[\n";
+      for (size_t i = 0; i < v.arr.size(); ++i) { o += pad; serialize_to(v.arr[i], o, depth + 1); o += i + 1 < v.arr.size() ? ",\n" : "\n"; }
+      o += close + "]";
+      break;
+    case Value::Object:
+      if (v.obj.empty()) { o += "{}"; break; }
+      o += "{\n";
+      for (size_t i = 0; i < v.obj.size(); ++i) {
+        o += pad + quoted(v.obj[i].first) + ": ";
+        serialize_to(v.obj[i].second, o, depth + 1);
+        o += i + 1 < v.obj.size() ? ",\n" : "\n";
+      }
+      o += close + "}";
+      break;
+  }
+}
+inline std::string serialize(const Value& v) { std::string o; serialize_to(v, o, 0); o.push_back('\n'); return o; }
+inline Value make_string(const std::string& s) { Value v; v.type = Value::String; v.s = s; return v; }
+inline Value make_int(int64_t i) { Value v; v.type = Value::Int; v.i = i; return v; }
+inline Value make_array() { Value v; v.type = Value::Array; return v; }
+inline Value make_object() { Value v; v.type = Value::Object; return v; }
 
 }  // namespace mini_json

@@ -255,8 +255,10 @@ GDB_HD bool imp_deletion_indel(const char* text, ImpTok ref, ImpTok alt) {
   return false;
 }
 
-// column and END of a record line; returns ImpErr bits (0: fine)
-GDB_HD uint32_t imp_coords(const ImpTables& T, const ImpLine& L, int64_t* col_out, int64_t* end_out) {
+// CHROM, POS and INFO END of a record line - the parse that the importer (imp_coords) and the splitter (core/gdb_split.hpp) share.
+// col = contig offset + POS - 1; *has_end: INFO carries END (the last one counts), then *end = contig offset + END - 1, else *end = col.
+// Returns IMP_ERR_SHORT_LINE, IMP_ERR_CONTIG or IMP_ERR_COORD_TEXT (0: fine)
+GDB_HD uint32_t imp_coords_text(const ImpTables& T, const ImpLine& L, int64_t* col_out, int64_t* end_out, bool* has_end) {
   if (imp_num_columns(L) < 8u) return IMP_ERR_SHORT_LINE;
   const char* text = L.text;
   const ImpTok chrom = imp_column(L, 0);
@@ -271,10 +273,24 @@ GDB_HD uint32_t imp_coords(const ImpTables& T, const ImpLine& L, int64_t* col_ou
   const int64_t col = offset + v - 1;
   int64_t end = col;
   ImpTok endv;
-  if (imp_info_find(text, imp_column(L, 7), "END", 3u, &endv)) {
+  *has_end = imp_info_find(text, imp_column(L, 7), "END", 3u, &endv);
+  if (*has_end) {
     if (!imp_parse_int(text + endv.b, endv.n(), &v)) return IMP_ERR_COORD_TEXT;
     end = offset + v - 1;
-  } else if (T.treat_deletions_as_intervals) {
+  }
+  *col_out = col;
+  *end_out = end;
+  return 0;
+}
+
+// column and END of a record line; returns ImpErr bits (0: fine)
+GDB_HD uint32_t imp_coords(const ImpTables& T, const ImpLine& L, int64_t* col_out, int64_t* end_out) {
+  int64_t col = 0, end = 0;
+  bool has_end = false;
+  const uint32_t e = imp_coords_text(T, L, &col, &end, &has_end);
+  if (e) return e;
+  const char* text = L.text;
+  if (!has_end && T.treat_deletions_as_intervals) {
     const ImpTok ref = imp_column(L, 3), alt = imp_column(L, 4);
     if (!imp_is_dot(text, alt)) {
       uint32_t at = alt.b;

@@ -35,7 +35,8 @@ struct ImportTablesHost {
 };
 
 // same walk over the schema as import_callsets_to_cells; what the bodies do not cover is refused by name
-inline ImportTablesHost build_import_tables(const VidMapper& vid) {
+// contigs_only: for a caller that reads nothing but CHROM, POS and END of a line (the splitter): no field is looked at, none refused
+inline ImportTablesHost build_import_tables(const VidMapper& vid, bool contigs_only = false) {
   if (!vid.is_initialized() || !vid.is_callset_mapping_initialized()) throw VCF2BinaryException("vid and callset mappings are needed");
   ImportTablesHost H;
   H.has_id = vid.get_field_info("ID") != nullptr;
@@ -51,7 +52,7 @@ inline ImportTablesHost build_import_tables(const VidMapper& vid) {
     if (f.is_flattened_field()) throw VCF2BinaryException("field " + f.m_name + ": flattened tuple elements are not imported by the device importer of this build (the host importer takes this vid)");
     if (f.m_num_dimensions == 2) throw VCF2BinaryException("field " + f.m_name + ": 2-dimensional (allele-specific) fields are not imported by the device importer of this build (the host importer takes this vid)");
   };
-  for (unsigned i = 0; i < vid.get_num_fields(); ++i) {
+  for (unsigned i = 0; i < vid.get_num_fields() && !contigs_only; ++i) {
     const FieldInfo& f = vid.get_field_info(i);
     if (f.m_name == "END") continue;
     const GdbCombineOp op = f.m_VCF_field_combine_operation;
@@ -64,7 +65,7 @@ inline ImportTablesHost build_import_tables(const VidMapper& vid) {
     }
     if (f.m_is_vcf_INFO_field) { refuse_2d(f); H.info.push_back(attr_of(f, sum_like)); H.info_names.push_back(f.m_name); }
   }
-  for (unsigned i = 0; i < vid.get_num_fields(); ++i) {
+  for (unsigned i = 0; i < vid.get_num_fields() && !contigs_only; ++i) {
     const FieldInfo& f = vid.get_field_info(i);
     if (f.m_name != "END" && f.m_is_vcf_FORMAT_field) { refuse_2d(f); H.fmt.push_back(attr_of(f, false)); H.fmt_names.push_back(f.m_name); }
   }

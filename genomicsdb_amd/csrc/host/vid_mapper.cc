@@ -268,7 +268,45 @@ void VidMapper::parse_callsets_json(const mini_json::Value& doc) {
     if (!l.IsArray()) throw VidMapperException(std::string("\"") + key + "\" must be a list of file names");
     for (size_t i = 0; i < l.Size(); ++i) m_csv_files[l[i].GetString()] = sorted ? GDB_FILE_SORTED_CSV : GDB_FILE_UNSORTED_CSV;
   }
+  if (lists.HasMember("split_files_paths")) {       // (reference vid_mapper.cc:908-945)
+    const mini_json::Value& d = lists["split_files_paths"];
+    if (!d.IsObject()) throw VidMapperException("\"split_files_paths\" must be a dictionary { original file : [ split paths ] | split path }");
+    for (size_t i = 0; i < d.obj.size(); ++i) {
+      const std::string& original = d.obj[i].first;
+      const mini_json::Value& v = d.obj[i].second;
+      if (m_split_files_paths.count(original)) throw VidMapperException("File " + original + " listed multiple times inside \"split_files_paths\" in the callsets mapping file");
+      SplitPaths sp;
+      if (v.IsString()) { sp.single = true; sp.paths.push_back(v.GetString()); }
+      else if (v.IsArray()) for (size_t k = 0; k < v.Size(); ++k) sp.paths.push_back(v[k].GetString());
+      else throw VidMapperException("\"split_files_paths\" entry of " + original + " must be a list of paths or one path");
+      m_split_files_paths[original] = sp;
+    }
+  }
   m_is_callset_mapping_initialized = true;
+}
+
+std::string VidMapper::get_split_file_path(const std::string& original_filename, const std::string& results_directory, int partition, const std::string& resolved_path) const {
+  auto it = m_split_files_paths.find(original_filename);
+  if (it != m_split_files_paths.end() && !it->second.paths.empty()) {
+    const SplitPaths& sp = it->second;
+    if (sp.single) return sp.paths[0];
+    if (partition < 0 || (size_t)partition >= sp.paths.size())
+      throw VidMapperException("Split files entry for file " + original_filename + " had " + std::to_string(sp.paths.size()) +
+                               " entries in the callset mapping JSON; however, entry with index " + std::to_string(partition) + " is requested");
+    return sp.paths[(size_t)partition];
+  }
+  // dirname / basename of the original, as the C library's functions give them for a path without a trailing '/'
+  const std::string& from = resolved_path.empty() ? original_filename : resolved_path;
+  const size_t slash = from.rfind('/');
+  const std::string dir = slash == std::string::npos ? "." : slash == 0 ? "/" : from.substr(0, slash);
+  const std::string base = slash == std::string::npos ? from : from.substr(slash + 1);
+  return (results_directory.empty() ? dir : results_directory) + "/partition_" + std::to_string(partition) + "_" + base;
+}
+
+void VidMapper::set_single_split_file_path(const std::string& original_filename, const std::string& path) {
+  SplitPaths sp;
+  sp.single = true; sp.paths.push_back(path);
+  m_split_files_paths[original_filename] = sp;
 }
 
 std::vector<std::string> VidMapper::schema_attribute_names() const {

@@ -80,6 +80,13 @@ class VidMapper {
   const std::vector<CallSetInfo>& get_callsets() const { return m_callsets; }   // mapping order
   // by the callsets' "filename" string; a name in a CSV list that no callset uses is ignored
   GdbFileType get_file_type(const std::string& filename) const { auto it = m_csv_files.find(filename); return it == m_csv_files.end() ? GDB_FILE_VCF : it->second; }
+  // where partition `partition` of input file `original_filename` is written by the splitter (reference vid_mapper.cc:512-574,
+  // VidMapper::get_split_file_path): the callset mapping's "split_files_paths" entry of the file - { original : [ path per partition ] }
+  // or { original : single path } - when there is one (an index past the list is an error), else
+  // <results_directory, or the original's directory>/partition_<partition>_<the original's basename>
+  // resolved_path: where the original is read from when its name is relative to a file root (the directory rule then follows the file)
+  std::string get_split_file_path(const std::string& original_filename, const std::string& results_directory, int partition, const std::string& resolved_path = "") const;
+  void set_single_split_file_path(const std::string& original_filename, const std::string& path);      // --split-output-filename
   // attribute order of the array schema (reference vid_mapper.cc:354-442): END, REF, ALT, [ID], QUAL, FILTER, INFO.., FORMAT..
   std::vector<std::string> schema_attribute_names() const;
  private:
@@ -91,6 +98,8 @@ class VidMapper {
   std::vector<std::string> m_row_idx_to_name;
   std::vector<CallSetInfo> m_callsets;
   std::unordered_map<std::string, GdbFileType> m_csv_files;
+  struct SplitPaths { bool single = false; std::vector<std::string> paths; };
+  std::unordered_map<std::string, SplitPaths> m_split_files_paths;
   bool m_is_initialized = false, m_is_callset_mapping_initialized = false;
 };
 

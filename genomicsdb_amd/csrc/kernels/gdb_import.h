@@ -12,6 +12,7 @@
 // (column, row) with ties in append order, gathers them into column-major order and copies the result out once.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -20,12 +21,34 @@
 
 namespace genomicsdb_amd {
 
+namespace gdbimp { struct ImpTables; }      // core/gdb_import.hpp
+
+// A text tap takes the importer's batches in place of the cells (kernels/gdb_split.hip): the same files, windows, batch cuts and
+// newline / tab index, then on_batch instead of measure and write.  Every pointer of a batch is device memory that is valid until
+// on_batch returns; the index is queued on `stream` (a hipStream_t), on which on_batch queues its own work.
+struct ImportTextBatch {
+  const std::string* path;                      // the file, for messages
+  const char* d_text;                           // n_bytes of whole lines (the last one ends with a newline), padded for 16-byte loads
+  const uint32_t* d_nl; const uint32_t* d_first_tab; const uint32_t* d_tab;      // the index: newline positions, tabs in front of a line, tab positions
+  uint32_t n_bytes, n_lines;
+  int64_t lines_before;                         // physical lines of the file in front of the batch
+  const gdbimp::ImpTables* tables;              // the contigs of the vid, in device memory (the struct itself is the host's)
+  void* stream;
+  std::function<std::string(uint32_t bit, uint32_t line)> describe;      // the words of an ImpErr bit raised on a line of the batch
+};
+struct ImportTextTap {
+  std::function<void(const std::string& path, const std::string& head)> on_header;      // a file's lines in front of its first record line
+  std::function<void(const ImportTextBatch&)> on_batch;
+};
+
 class DeviceImporter {
  public:
   static constexpr uint64_t kDefaultTextBudget = (uint64_t)64 << 20;
   // refuses (VCF2BinaryException) what the bodies do not cover before anything is launched
   enum { kInflateAuto = 0, kInflateHost = 1, kInflateDevice = 2 };      // BGZF on the device else the host; always the host; a file that is not BGZF is an error
-  DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes = 0, int inflate_mode = kInflateAuto);
+  // tap: see ImportTextTap; with one, only the contigs of the vid are needed (no field is refused), finish() has nothing to give
+  DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes = 0, int inflate_mode = kInflateAuto,
+                 const ImportTextTap* tap = nullptr);
   ~DeviceImporter();
   DeviceImporter(const DeviceImporter&) = delete;
   DeviceImporter& operator=(const DeviceImporter&) = delete;
@@ -33,6 +56,8 @@ class DeviceImporter {
   void import_all(const std::vector<ImportStream>& streams = std::vector<ImportStream>());
   // a "filename" of the callset mapping.  The content decides: VCF text or BCF2 ('BCF\2\1' / 'BCF\2\2'), plain, gzip or BGZF
   void append_file(const std::string& filename);
+  // with a tap: a file of VCF text (plain, gzip or BGZF) by its path, in the callset mapping or not
+  void append_text_path(const std::string& path);
   // the same from memory (the buffer-stream input of the reference's importer): `name` is a "filename" of the callset mapping whose
   // content is the nbytes at ptr, sniffed like a file's
   void append_buffer(const std::string& name, const void* ptr, uint64_t nbytes);

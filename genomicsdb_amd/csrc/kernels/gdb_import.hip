@@ -51,29 +51,17 @@
 #include "../common/gz_text.hpp"
 #include "../host/import_bcf.hpp"
 #include "../host/import_common.hpp"
+#include "gdb_import_device.hpp"
 #include "gdb_inflate.h"
 #include "gdb_pipeline.h"
 
 namespace genomicsdb_amd {
 
-#define IMP_HIP_CHECK(expr)                                                                                        \
-  do {                                                                                                             \
-    hipError_t _e = (expr);                                                                                        \
-    if (_e != hipSuccess)                                                                                          \
-      throw GenomicsDBDeviceException(std::string(#expr) + " failed: " + hipGetErrorString(_e) + " at " + __FILE__ + ":" + std::to_string(__LINE__)); \
-  } while (0)
-
 namespace {
 using namespace gdbimp;
+using namespace impdev;
 
-constexpr int kBlock = 256;              // 4 wavefronts
-constexpr int kBytesPerThread = 16;      // one 16-byte load
-constexpr uint32_t kTile = kBlock * kBytesPerThread;
-constexpr uint32_t kTextPad = 64;        // bytes behind the text that the 16-byte loads may touch
-constexpr int kErrWords = 20;            // [0]: ImpErr bits, [1 + b]: smallest line that raised bit b
 constexpr uint64_t kDroppedKey = ~(uint64_t)0;
-
-struct ImpBatch { const char* text; const uint32_t* nl_pos; const uint32_t* line_first_tab; const uint32_t* tab_pos; uint32_t n_lines; };
 
 // counts of one thread's 16 bytes: newlines in the high word, tabs in the low word
 __device__ __forceinline__ uint64_t imp_count16(const char* text, uint32_t n, uint64_t at, uint4* bytes) {
@@ -143,23 +131,6 @@ __global__ void __launch_bounds__(kBlock) k_imp_find_chrom(const char* text, uin
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i + 6u > n || text[i] != '#' || (i > 0 && text[i - 1u] != '\n')) return;
   if (text[i + 1u] == 'C' && text[i + 2u] == 'H' && text[i + 3u] == 'R' && text[i + 4u] == 'O' && text[i + 5u] == 'M') *found = 1u;
-}
-
-__device__ __forceinline__ ImpLine imp_line_of(const ImpBatch& B, uint32_t line) {
-  ImpLine L;
-  L.text = B.text;
-  L.begin = line ? B.nl_pos[line - 1u] + 1u : 0u;
-  L.end = B.nl_pos[line];
-  if (L.end > L.begin && B.text[L.end - 1u] == '\r') --L.end;
-  const uint32_t first = B.line_first_tab[line];
-  L.tabs = B.tab_pos + first;
-  L.ntabs = B.line_first_tab[line + 1u] - first;
-  return L;
-}
-
-__device__ __forceinline__ void imp_raise(uint32_t* err, uint32_t bits, uint32_t line) {
-  atomicOr(&err[0], bits);
-  for (uint32_t b = 0; b < (uint32_t)kErrWords - 1u; ++b) if (bits & (1u << b)) atomicMin(&err[1u + b], line);
 }
 
 struct ImpSamples { const int32_t* file_idx; const int64_t* row; int32_t n; };    // imported samples of the file
@@ -346,21 +317,6 @@ __global__ void __launch_bounds__(kBlock) k_imp_gather(const uint32_t* idx, cons
   for (uint32_t i = lane; i < n; i += 64u) out[at + i] = from[i];
 }
 
-template <class T> struct DBuf {       // grow-only device block
-  T* p = nullptr; size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    IMP_HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
-    cap = n;
-  }
-  ~DBuf() { if (p) (void)hipFree(p); }
-};
-template <class T> T* dalloc(size_t n) { T* p = nullptr; IMP_HIP_CHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); return p; }
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 struct DeviceImporter::Impl {
@@ -379,6 +335,7 @@ struct DeviceImporter::Impl {
   DBuf<uint32_t> d_err, d_ndef;
   bool spanning = false; int seq_bits = 64; uint64_t line_seq = 0;
   bool spanning_slots = false;       // a batch whose slots take part in the partition-begin rule was queued (never a CSV batch)
+  ImportTextTap tap; bool tapped = false;      // tapped: text batches go to tap.on_batch once indexed, no cell is made
   bool stage_in_lds = true;          // the A/B of profiles/device_import.md: -7.5 % on the write kernel; GDBAMD_IMPORT_STAGE_LDS=0|1 overrides
   // per batch, reused
   DBuf<char> d_text, d_tmp;
@@ -424,6 +381,7 @@ struct DeviceImporter::Impl {
   // n_csv_rows >= 0: the lines are those of a CSV cell file, and d_samp_row holds that many rows of the file, ascending
   uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp, int n_csv_rows = -1);
   int upload_samples(const ImportHeader& hdr);                              // -> imported samples of the file
+  void append_vcf_path(const ImportFile& file, double t0);                  // a file of VCF text: BGZF to the device as it is, else inflated here
   void append_text(const ImportFile& file, const std::string& text);        // inflated text of a whole file, on the host
   void append_bgzf(const ImportFile& file, const std::string& raw, const std::vector<BgzfMember>& mem);
   void append_bcf(const ImportFile& file, const char* data, size_t n);      // a whole BCF2 stream, inflated
@@ -440,8 +398,11 @@ struct DeviceImporter::Impl {
   void find_newlines(const char* text, uint64_t lo, uint64_t mid, uint64_t hi, uint64_t* last_below, uint64_t* first_above);
 };
 
-DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes, int inflate_mode) : m_(new Impl) {
+DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes, int inflate_mode, const ImportTextTap* tap)
+    : m_(new Impl) {
   try {
+    if (tap) m_->tap = *tap;
+    m_->tapped = tap != nullptr;
     if (inflate_mode < kInflateAuto || inflate_mode > kInflateDevice) throw VCF2BinaryException("inflate mode " + std::to_string(inflate_mode) + ": 0 (auto), 1 (host) or 2 (device)");
     m_->inflate_mode = inflate_mode;
     m_->device = device;
@@ -451,14 +412,14 @@ DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOpt
     if (const char* e = getenv("GDBAMD_IMPORT_STAGE_LDS")) m_->stage_in_lds = atoi(e) != 0;
     // the A/B of profiles/device_inflate.md: one thread per BGZF member instead of one wavefront (9.6 x slower; kept for that comparison)
     if (const char* e = getenv("GDBAMD_INFLATE_KERNEL")) m_->inflater.set_kernel(std::string(e) == "thread" ? BgzfDeviceInflater::kThreadPerMember : BgzfDeviceInflater::kWavePerMember);
-    m_->H = build_import_tables(vid);                 // the refusals: before the device is touched
+    m_->H = build_import_tables(vid, m_->tapped);     // the refusals: before the device is touched (a tap copies lines: contigs only)
     m_->files = import_files(vid, m_->opt);
     for (const CallSetInfo& cs : vid.get_callsets()) {
       bool used = false;
       for (const ImportFile& f : m_->files) used = used || f.name == cs.m_filename;
       if (!used) m_->skipped_files.push_back(cs.m_filename);
     }
-    refuse_for_csv(vid, m_->H, m_->files);
+    if (!m_->tapped) refuse_for_csv(vid, m_->H, m_->files);
     Impl& M = *m_;
     if (opt.column_begin > 0) {
       int col_bits = 0;
@@ -572,6 +533,22 @@ void DeviceImporter::append_file(const std::string& filename) {
     M.append_bcf(*file, data.data(), data.size());
     return;
   }
+  M.append_vcf_path(*file, t0);
+}
+
+void DeviceImporter::append_text_path(const std::string& path) {
+  Impl& M = *m_;
+  if (!M.tapped) throw VCF2BinaryException("append_text_path needs a text tap: " + path + " has no callset to make cells for");
+  IMP_HIP_CHECK(hipSetDevice(M.device));
+  ImportFile file;
+  file.name = path; file.path = path;
+  for (const ImportFile& f : M.files) if (f.path == path) file = f;
+  M.append_vcf_path(file, now_s());
+}
+
+void DeviceImporter::Impl::append_vcf_path(const ImportFile& file_, double t0) {
+  Impl& M = *this;
+  const ImportFile* file = &file_;
   std::string raw;
   std::vector<BgzfMember> mem;
   bool is_bgzf = false;
@@ -631,6 +608,7 @@ void DeviceImporter::Impl::append_text(const ImportFile& file_, const std::strin
   Impl& M = *this;
   const ImportHeader hdr = parse_import_header(text, *file);
   const int n_imp = upload_samples(hdr);
+  if (tapped && tap.on_header) tap.on_header(file->path, text.substr(0, hdr.record_begin));
   // batches of at most the budget, cut behind a newline; a line longer than the budget grows its batch
   size_t pos = hdr.record_begin;
   int64_t lines_before = hdr.lines_before;
@@ -696,6 +674,7 @@ void DeviceImporter::Impl::append_bgzf(const ImportFile& file, const std::string
   st.s_read += now_s() - t0;
   const ImportHeader hdr = parse_import_header(head, file);
   const int n_imp = upload_samples(hdr);
+  if (tapped && tap.on_header) tap.on_header(file.path, head.substr(0, hdr.record_begin));
   const std::string chrom_error = "a #CHROM line after the first record in " + file.path + " is not imported by the device importer of this build";
 
   // ---- windows: [carried partial line | members k .. k2)
@@ -842,6 +821,16 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
     le = std::min<uint32_t>(le, (uint32_t)n_text);
     return describe_line_error(bit, H, opt, hdr, host_text(), lb, le, words.where(line));
   };
+  if (tapped) {       // the indexed batch is the product
+    ImportTextBatch b;
+    b.path = &file.path; b.d_text = d_text.p; b.d_nl = d_nl.p; b.d_first_tab = d_first_tab.p; b.d_tab = d_tab.p;
+    b.n_bytes = n; b.n_lines = n_lines; b.lines_before = lines_before; b.tables = &T; b.stream = (void*)stream; b.describe = words.describe;
+    if (tap.on_batch) tap.on_batch(b);
+    IMP_HIP_CHECK(hipStreamSynchronize(stream));
+    float ms = 0;
+    IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1])); st.ms_index += ms;
+    return n_lines;
+  }
   cells_of_batch(ImpTextSrc{{}, ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}}, T, n_lines, n_imp, words);
   return n_lines;
 }

@@ -319,6 +319,25 @@ int gdbamd_import_cells_device_rows(const char* vid_mapping_file, const char* ca
 #define GDBAMD_MERGE_NUM_STATS 12
 int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nbytes, uint8_t** cells, uint64_t* out_nbytes, int64_t* ncells, int device,
                        double* stats, int nstats);
+/* vcf2tiledb --split-files on GPU `device` (kernels/gdb_split.hip; reference tools/src/vcf2tiledb.cc:118-151): every (g)VCF text file of the callset
+ * mapping - plain, gzip or BGZF; then the nextra paths of extra_paths - is cut into one BGZF file + <file>.tbi per column partition, in one pass per file.
+ * Partition p is [begins[p], ends[p]] (the loader JSON's column_partitions with derived ends; they must not overlap, at most 4096).  A partition's file holds
+ * every '#' line and, in file order and verbatim, every record line whose interval overlaps the partition: [col, tend], col = contig offset + POS - 1,
+ * tend = contig offset + END - 1 with INFO END (the last END counts), else col + len(REF) - 1.  A line that spans partitions goes to each; a partition
+ * without records still gets the header, the EOF block and an index.  produce: the one partition index to write, or -1 for all.  An output is
+ * <results_directory, or the input's directory>/partition_<p>_<the input's basename> unless the callset mapping's "split_files_paths" names it;
+ * single_output_name (NULL / "": none) names the output of exactly one input and one partition.  Errors that name file and 1-based line: a contig that is
+ * not in the vid, POS / END that is no plain integer, fewer than 8 columns; BCF2 and CSV inputs are refused by name before anything runs.  After an error
+ * no output of the failing input exists.  text_budget_bytes and inflate_mode as for gdbamd_import_cells_device_ex.
+ * *outputs (may be NULL) receives one line "original filename \t partition \t path \n" per file written, malloc'ed: release with gdbamd_free.
+ * stats: NULL or nstats doubles:
+ *   0 files, 1 record lines, 2 record lines written (summed over the partitions), 3 text bytes in, 4 text bytes out, 5 compressed bytes out, 6 batches,
+ *   7..10 HIP-event ms of index / classify / scan + gather / deflate, 11..15 wall seconds of file read, H2D, D2H + write, .tbi build, total,
+ *   16 HIP-event ms of the BGZF inflate kernel */
+#define GDBAMD_SPLIT_NUM_STATS 17
+int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
+                              const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
+                              uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs);
 void gdbamd_free(void* p);
 
 #ifdef __cplusplus
