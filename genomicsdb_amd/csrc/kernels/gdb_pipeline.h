@@ -42,6 +42,8 @@ struct IntervalStats {
   uint64_t bytes_compressed = 0;   // BGZF output formats: bytes of the pages after compression (bytes_out stays the uncompressed size)
   float ms_compress = 0;           // device time of the compression kernels
   int page_kernel = 0;             // digits S K W C II of the most recent page launch (see include/genomicsdb_amd.h), set at the launch sites; 0: no page yet
+  int huge_records = 0;            // records whose call walk the workgroup-per-record site kernel (k_site_huge) was given; 0: not launched
+  int huge_fallbacks = 0;          // ... of which it handed back to the serial walk (hash collision, table overflow, several FILTER ids)
   // the reference's GTProfileStats counters (query_variants.h:67-124), per interval; see include/genomicsdb_amd.h
   uint64_t gt_profile[6] = {0, 0, 0, 0, 0, 0};
 };

@@ -560,7 +560,7 @@ __device__ uint32_t huge_tie_median(const uint32_t* __restrict__ val, int64_t hb
   return r;
 }
 __global__ void __launch_bounds__(kHugeBlock) k_site_huge(const SiteCtx* __restrict__ sxp, const int32_t* __restrict__ huge_list, const int32_t* __restrict__ counter,
-                                                      HugeSiteOut* __restrict__ out, uint32_t* err) {
+                                                      HugeSiteOut* __restrict__ out, uint32_t* err, int32_t* fallbacks) {
   const SiteCtx& cx = *sxp;
   const CombinePlan& pl = cx.pl;
   __shared__ uint32_t tab_hash[kHugeTable], tab_order[kHugeTable];
@@ -684,6 +684,7 @@ __global__ void __launch_bounds__(kHugeBlock) k_site_huge(const SiteCtx* __restr
       o.filter_first_id = (do_filter && s_filter != ~0ull) ? (int32_t)(uint32_t)s_filter : -1;
       o.filter_multi = s_flags[2]; o.any_id = s_flags[3];
       o.fallback = (s_flags[0] || s_flags[1] || s_flags[2]) ? 1 : 0;   // several different FILTER ids: their order needs the calls in sequence (filter_union_order)
+      if (o.fallback) atomicAdd(fallbacks, 1);                         // (IntervalStats::huge_fallbacks)
     }
     // ---- scalar reducers over the gathered per-call values (ScalarPre) ---------------------------------------------------------------
     if (cx.pre.enabled)
@@ -5674,7 +5675,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     HIP_CHECK(hipMemcpyAsync(S.d_sx0.p, &sx0, sizeof(SiteCtx), hipMemcpyHostToDevice, st));
     STAGE("k_site_huge");
     hipLaunchKernelGGL(k_huge_records, dim3(blocks_for(P)), dim3(kBlock), 0, st, (const int64_t*)S.hbase.p, P, huge_threshold, S.huge_index.p, S.huge_list.p, S.counters.p + 3);
-    hipLaunchKernelGGL(k_site_huge, dim3(1024), dim3(kHugeBlock), 0, st, (const SiteCtx*)S.d_sx0.p, (const int32_t*)S.huge_list.p, (const int32_t*)(S.counters.p + 3), S.huge_out.p, S.err.p);
+    hipLaunchKernelGGL(k_site_huge, dim3(1024), dim3(kHugeBlock), 0, st, (const SiteCtx*)S.d_sx0.p, (const int32_t*)S.huge_list.p, (const int32_t*)(S.counters.p + 3), S.huge_out.p, S.err.p, S.counters.p + 6);
     huge.index = S.huge_index.p; huge.out = S.huge_out.p; huge.enabled = 1;
   }
   SiteCtx sx{fr, pl, cm, rec, hl, pc, nt, qw, so, med, big, tie, pre, huge};
@@ -5735,8 +5736,11 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   S.excl_scan(S.nslots.p, S.tbase.p, (size_t)CW);
   uint32_t ur_a = 0, ur_b = 0, sl_a = 0, sl_b = 0;
   int32_t ntypes = 0;
+  int32_t huge_counts[4] = {0, 0, 0, 0};      // counters[3]: records k_huge_records listed, counters[6]: the ones k_site_huge handed back (0 when not launched)
   S.read_back_many({{&ur_a, S.ubase.p + (P - 1), 4}, {&ur_b, S.untabled.p + (P - 1), 4}, {&sl_a, S.tbase.p + (CW - 1), 4}, {&sl_b, S.nslots.p + (CW - 1), 4},
-                    {&ntypes, S.counters.p + 1, 4}});
+                    {&ntypes, S.counters.p + 1, 4}, {huge_counts, S.counters.p + 3, sizeof(huge_counts)}});
+  stats.huge_records = std::min(huge_counts[0], (int32_t)kMaxHugeRecords);
+  stats.huge_fallbacks = huge_counts[3];
   const int64_t UR = (int64_t)ur_a + ur_b;
   const uint64_t SL = (uint64_t)sl_a + sl_b;
   if (UR > 0) hipLaunchKernelGGL(k_untabled_records, dim3(blocks_for(P)), dim3(kBlock), 0, st, S.untabled.p, S.ubase.p, P, S.urec.p);

@@ -114,6 +114,10 @@ typedef struct gdbamd_interval_stats {
    * VALID_CELLS_IN_QUERY = cells that contribute to at least one record, ATTR_CELLS_ACCESSED = those x queried attributes,
    * PQ_FLUSHES_DUE_TO_OVERLAPPING_CELLS = cells cut short by the next cell of their own sample, OPERATOR_INVOCATIONS = records */
   uint64_t gt_profile_stats[6];
+  int32_t huge_records;                  /* records with so many variant calls (more than 256; more than 24 when the interval averages 24 and more per
+                                          * record) that one workgroup each did their call walk (k_site_huge); 0 when that kernel was not launched */
+  int32_t huge_fallbacks;                /* ... of which the kernel handed back to the one-thread walk: two alleles with one 32-bit hash, a full allele
+                                          * table, several different FILTER ids */
 } gdbamd_interval_stats;
 enum { GDBAMD_GT_NUM_CELLS = 0, GDBAMD_GT_NUM_CELLS_IN_LEFT_SWEEP, GDBAMD_GT_NUM_VALID_CELLS_IN_QUERY, GDBAMD_GT_NUM_ATTR_CELLS_ACCESSED,
        GDBAMD_GT_NUM_PQ_FLUSHES_DUE_TO_OVERLAPPING_CELLS, GDBAMD_GT_NUM_OPERATOR_INVOCATIONS, GDBAMD_GT_NUM_STATS };

@@ -57,10 +57,12 @@ def test_more_than_sixteen_ids_is_reported():
     assert n == -1
 
 
-def _two_filter_cells(tmp_path, N=300, L=1200, seed=5):
+def _two_filter_cells(tmp_path, N=300, L=1200, seed=5, hot=None):
+    """hot = (offset, length, stride, K): a region where the samples start insertions at every multiple of stride (synth.Generator's dense)"""
     from genomicsdb_amd import synth
     B = 10_000_000
-    g = synth.Generator(N, B, L + 2500, seed=seed, filter_permille=350, filter2_permille=350, filter_id=1, filter_id2=0, rank_sum_scale=10.0)
+    g = synth.Generator(N, B, L + 2500, seed=seed, dense=(B + hot[0],) + tuple(hot[1:]) if hot else None, filter_permille=350, filter2_permille=350,
+                        filter_id=1, filter_id2=0, rank_sum_scale=10.0)
     cells, _ = g.chunk_bytes(B + L + 2500)
     q = helpers.synth_query(tmp_path, N, B + 20, B + L)
     q["produce_FILTER_field"] = True
@@ -80,19 +82,26 @@ def test_kernel_bodies_write_multi_id_unions_like_the_oracle(tmp_path):
 @pytest.mark.parametrize("n_samples", [300, 1200])
 def test_device_writes_multi_id_unions_like_the_oracle(tmp_path, n_samples):
     """1 200 samples: records with more than 256 variant calls go through the workgroup-per-record site kernel, which hands a
-    record with several ids back to the serial walk"""
+    record with several ids back to the serial walk.  (Without the hot region no record of this input has more than 8 variant calls and
+    the kernel never runs: the two sites of the region have 426 and 685, both with both ids.)"""
     import genomicsdb_amd
     from genomicsdb_amd import synth
     L = 1200 if n_samples < 1000 else 300
-    B, cells, q = _two_filter_cells(tmp_path, N=n_samples, L=L, seed=9)
+    B, cells, q = _two_filter_cells(tmp_path, N=n_samples, L=L, seed=9, hot=(100, 100, 50, 8) if n_samples == 1200 else None)
     want, nrec, _ = helpers.oracle_run_synth(q, cells, 9, with_header=False)
     assert sum(1 for l in want.split(b"\n") if l and b";" in l.split(b"\t")[6]) >= 3
+    if n_samples == 1200:     # a record that unites two ids over more than 256 variant calls (the samples that carry AD) exists
+        f = [l.split(b"\t") for l in want.split(b"\n") if l.startswith(b"1\t%d\t" % (B + 151))][0]
+        ad = f[8].split(b":").index(b"AD")
+        assert b";" in f[6] and sum(1 for s in f[9:] if s.count(b":") >= ad and s.split(b":")[ad] != b".") > 256
     e = genomicsdb_amd.CombineEngine(q)
     e.stage_cells(cells)
     e.set_reference(B, synth.reference(B, L + 4096, seed=9))
     body, st = e.run_interval(B + 20, B + L, arena_bytes=1 << 22)
     e.close()
     assert st.num_records == nrec and body == want
+    if n_samples == 1200:
+        assert st.huge_fallbacks >= 1             # the workgroup kernel ran and handed records with several ids back
     eb = genomicsdb_amd.CombineEngine(q, is_bcf=True)
     eb.stage_cells(cells)
     eb.set_reference(B, synth.reference(B, L + 4096, seed=9))
