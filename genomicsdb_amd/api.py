@@ -414,6 +414,120 @@ def import_cells(vid_mapping_file, callset_mapping_file, file_root="", treat_del
         L.gdbamd_free(p)
 
 
+STREAM_IMPORT_STAT_NAMES = ("num_batches", "num_records", "num_cells", "num_bytes", "max_pending_cells", "max_pending_bytes", "num_deferred_values",
+                            "num_spanning_cells", "ms_order", "ms_classify", "ms_sort_gather", "ms_compact", "s_h2d", "s_d2h")
+
+
+class StreamImporter:
+    """The reference's GenomicsDBImporter protocol on one GPU (csrc/api/genomicsdb_importer.h, kernels/gdb_import_stream.hip): buffer
+    streams of VCF text or BCF2 records are imported batch by batch, with bounded device memory.
+
+        imp = StreamImporter(loader_json)                 # a path, or a dict / JSON text
+        imp.add_buffer_stream(name, is_bcf, capacity, header_bytes)       # once per stream
+        used = imp.setup(callsets_json)                   # -> per stream its index among the sources of the callset mapping, -1: unused
+        while not imp.done:
+            cells, exhausted = imp.import_batch()         # cells of this batch (column-major), [(stream, 0), ...] to refill
+            for idx, _ in exhausted:
+                imp.write(idx, whole_records)             # b"" (or no write) ends the stream
+        imp.finish()                                      # the loader's outputs, as vcf2tiledb makes them
+
+    The batches' cells, concatenated, are import_cells() of the same records.  A batch hands over every pending cell whose column is
+    strictly below W, the smallest last column over the streams that have not ended, and reports the streams whose last column is not
+    above W.  Errors (GenomicsDBException) name the stream and the record or byte offset; after one, the importer can only be closed."""
+
+    def __init__(self, loader_json, rank=0, device=0):
+        import json
+        self._L = _lib.lib()
+        self._n = 0
+        self._max = 0
+        text = json.dumps(loader_json) if isinstance(loader_json, dict) else loader_json
+        self._h = self._L.gdbamd_importer_create(os.fsencode(text), int(rank), int(device))
+        _check(self._h, "StreamImporter")
+
+    def _handle(self):
+        if not self._h:
+            raise GenomicsDBException("StreamImporter is closed")
+        return self._h
+
+    def add_buffer_stream(self, name, is_bcf, capacity, init=b""):
+        init = bytes(init)
+        _check(self._L.gdbamd_importer_add_buffer_stream(self._handle(), os.fsencode(name), 1 if is_bcf else 0, int(capacity), init, len(init)) == 0, "add_buffer_stream")
+        self._n += 1
+        return self._n - 1
+
+    def setup(self, callsets_json=""):
+        import json
+        text = json.dumps(callsets_json) if isinstance(callsets_json, dict) else (callsets_json or "")
+        n = ctypes.c_int64()
+        _check(self._L.gdbamd_importer_setup_loader(self._handle(), text.encode(), ctypes.byref(n)) == 0, "setup_loader")
+        self._max = n.value
+        out = []
+        for i in range(self._n):
+            f = ctypes.c_int64()
+            _check(self._L.gdbamd_importer_stream_file_idx(self._h, i, ctypes.byref(f)) == 0, "stream_file_idx")
+            out.append(f.value)
+        return out
+
+    @property
+    def max_identifiers(self):
+        return self._max
+
+    def write(self, idx, data, partition_idx=0):
+        data = bytes(data)
+        _check(self._L.gdbamd_importer_write(self._handle(), int(idx), int(partition_idx), data, len(data)) == 0, "write_data_to_buffer_stream")
+
+    def import_batch(self):
+        p = ctypes.c_void_p()
+        n = ctypes.c_uint64()
+        pairs = (ctypes.c_int64 * (2 * max(self._max, 1)))()
+        ne = ctypes.c_int64()
+        _check(self._L.gdbamd_importer_import_batch(self._handle(), ctypes.byref(p), ctypes.byref(n), pairs, ctypes.byref(ne)) == 0, "import_batch")
+        try:
+            cells = ctypes.string_at(p.value, n.value)
+        finally:
+            self._L.gdbamd_free(p)
+        return cells, [(pairs[2 * i], pairs[2 * i + 1]) for i in range(ne.value)]
+
+    @property
+    def done(self):
+        r = self._L.gdbamd_importer_is_done(self._handle())
+        _check(r >= 0, "is_done")
+        return r == 1
+
+    def finish(self):
+        _check(self._L.gdbamd_importer_finish(self._handle()) == 0, "finish")
+
+    def stats(self):
+        st = (ctypes.c_double * len(STREAM_IMPORT_STAT_NAMES))()
+        _check(self._L.gdbamd_importer_stats(self._handle(), st) == 0, "stats")
+        return {k: (float(v) if k[:2] in ("ms", "s_") else int(v)) for k, v in zip(STREAM_IMPORT_STAT_NAMES, st)}
+
+    def close(self):
+        if self._h:
+            self._L.gdbamd_importer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def chromosome_intervals(loader_json, rank=0):
+    """{"contigs": [{name: [begin, end]}, ...]}: the 1-based contig intervals that column partition `rank` of the loader JSON (a path, a
+    dict or JSON text) covers - what the reference's jniGetChromosomeIntervalsForColumnPartition returns; -> the JSON text"""
+    import json
+    text = json.dumps(loader_json) if isinstance(loader_json, dict) else loader_json
+    p = ctypes.c_void_p()
+    L = _lib.lib()
+    _check(L.gdbamd_chromosome_intervals_for_column_partition(os.fsencode(text), int(rank), ctypes.byref(p)) == 0, "chromosome_intervals")
+    try:
+        return ctypes.string_at(p.value).decode()
+    finally:
+        L.gdbamd_free(p)
+
+
 SPLIT_STAT_NAMES = ("num_files", "num_record_lines", "num_lines_written", "text_bytes_in", "text_bytes_out", "compressed_bytes_out", "num_batches", "ms_index",
                     "ms_classify", "ms_scan_gather", "ms_deflate", "s_read", "s_h2d", "s_d2h_write", "s_index_build", "s_total", "ms_inflate")
 

@@ -13,12 +13,13 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(PKG, "libgenomicsdb_amd.so")
 TOOL = os.path.join(PKG, "gt_mpi_gather")
-TOOLS = {"gt_mpi_gather": TOOL, "vcf2tiledb": os.path.join(PKG, "vcf2tiledb")}
+TOOLS = {"gt_mpi_gather": TOOL, "vcf2tiledb": os.path.join(PKG, "vcf2tiledb"), "test_genomicsdb_importer": os.path.join(PKG, "test_genomicsdb_importer")}
 
 SOURCES = [
     "kernels/gdb_pipeline.hip",
     "kernels/gdb_bgzf.hip",
     "kernels/gdb_import.hip",
+    "kernels/gdb_import_stream.hip",
     "kernels/gdb_inflate.hip",
     "kernels/gdb_merge.hip",
     "kernels/gdb_split.hip",
@@ -31,6 +32,8 @@ SOURCES = [
     "host/vcf_index.cc",
     "api/genomicsdb_bcf_generator.cc",
     "api/genomicsdb_operators.cc",
+    "api/genomicsdb_importer.cc",
+    "api/loader_outputs.cc",
     "api/capi.cc",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -83,8 +86,8 @@ def build_native(verbose=False):
 
 
 def build_jni(verbose=False):
-    """libtiledbgenomicsdb.so (the name the reference's Java loader asks for) = the GenomicsDBQueryStream natives and the
-    one-time initialiser over the C ABI.  Compiled against a JDK's jni.h when $JAVA_HOME has one, else against the minimal
+    """libtiledbgenomicsdb.so (the name the reference's Java loader asks for) = the GenomicsDBQueryStream natives, the
+    GenomicsDBImporter natives (jni_importer.cc) and the one-time initialiser over the C ABI.  Compiled against a JDK's jni.h when $JAVA_HOME has one, else against the minimal
     stand-in csrc/jni/stub/jni.h (specification function-table indices only), so the glue is built and symbol-checked always."""
     jh = os.environ.get("JAVA_HOME", "")
     inc = os.path.join(jh, "include") if jh else ""
@@ -93,9 +96,9 @@ def build_jni(verbose=False):
     else:
         incs = ["-I" + os.path.join(CSRC, "jni", "stub")]
     out = os.path.join(PKG, "libtiledbgenomicsdb.so")
-    src = os.path.join(CSRC, "jni", "jni_query_stream.cc")
-    if _newer(out, [src, LIB, os.path.join(CSRC, "jni", "stub", "jni.h"), os.path.join(ROOT, "include", "genomicsdb_amd.h")]):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + incs + [src, "-o", out, "-L" + PKG, "-lgenomicsdb_amd", "-Wl,-rpath,$ORIGIN"]
+    srcs = [os.path.join(CSRC, "jni", "jni_query_stream.cc"), os.path.join(CSRC, "jni", "jni_importer.cc")]
+    if _newer(out, srcs + [LIB, os.path.join(CSRC, "jni", "stub", "jni.h"), os.path.join(ROOT, "include", "genomicsdb_amd.h")]):
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + incs + srcs + ["-o", out, "-L" + PKG, "-lgenomicsdb_amd", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
@@ -139,6 +142,21 @@ def build_hostsim_import_csv():
     d = os.path.join(ROOT, "tests", "hostsim_import_csv")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "libhostsim_import_csv.so"), os.path.join(d, "hostsim_import_csv_main")
+
+
+def build_hostsim_import_stream():
+    """CPU harness around the bodies of the streaming importer (core/gdb_import_stream.hpp) and the same source as a stand-alone
+    program built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_import_stream")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_import_stream.so"), os.path.join(d, "hostsim_import_stream_main")
+
+
+def build_jni_importer_harness():
+    """JVM-less driver of the GenomicsDBImporter natives in libtiledbgenomicsdb.so (tests only); -> program"""
+    d = os.path.join(ROOT, "tests", "jni_importer_harness")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "jni_importer_harness")
 
 
 def build_hostsim_merge():

@@ -8,6 +8,8 @@
 #include <cstring>
 
 #include "genomicsdb_bcf_generator.h"
+#include "genomicsdb_importer.h"
+#include "../kernels/gdb_import_stream.h"
 #include "../kernels/gdb_bgzf.h"
 #include "../kernels/gdb_inflate.h"
 #include "../kernels/gdb_split.h"
@@ -579,6 +581,86 @@ int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_
     g_last_error.clear();
     return 0;
   } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
+// ---- the streaming importer (api/genomicsdb_importer.h)
+void* gdbamd_importer_create(const char* loader_json, int rank, int device) {
+  return guarded([&]() -> void* {
+    if (!loader_json) throw GenomicsDBConfigException("gdbamd_importer_create: null loader JSON");
+    return new GenomicsDBImporter(loader_json, rank, device);
+  }, (void*)nullptr);
+}
+static GenomicsDBImporter& importer_of(void* h) {
+  if (!h) throw GenomicsDBConfigException("null importer handle");
+  return *static_cast<GenomicsDBImporter*>(h);
+}
+int gdbamd_importer_add_buffer_stream(void* h, const char* name, int is_bcf, uint64_t capacity, const uint8_t* init, uint64_t init_nbytes) {
+  return guarded([&] {
+    if (!name) throw GenomicsDBConfigException("gdbamd_importer_add_buffer_stream: null name");
+    importer_of(h).add_buffer_stream(name, is_bcf ? BCF_BUFFER_STREAM_TYPE : VCF_BUFFER_STREAM_TYPE, (size_t)capacity, init, (size_t)init_nbytes);
+    return 0;
+  }, -1);
+}
+int gdbamd_importer_setup_loader(void* h, const char* callsets_json, int64_t* max_identifiers) {
+  return guarded([&] {
+    GenomicsDBImporter& imp = importer_of(h);
+    imp.setup_loader(callsets_json ? callsets_json : "");
+    if (max_identifiers) *max_identifiers = (int64_t)imp.get_max_num_buffer_stream_identifiers();
+    return 0;
+  }, -1);
+}
+int gdbamd_importer_stream_file_idx(void* h, int64_t stream_idx, int64_t* file_idx) {
+  return guarded([&] {
+    const std::vector<int64_t>& v = importer_of(h).get_buffer_stream_idx_to_global_file_idx_vec();
+    if (stream_idx < 0 || (size_t)stream_idx >= v.size() || !file_idx) throw GenomicsDBConfigException("gdbamd_importer_stream_file_idx: no such stream");
+    *file_idx = v[(size_t)stream_idx];
+    return 0;
+  }, -1);
+}
+int gdbamd_importer_write(void* h, int64_t stream_idx, unsigned partition_idx, const uint8_t* data, uint64_t nbytes) {
+  return guarded([&] { importer_of(h).write_data_to_buffer_stream(stream_idx, partition_idx, data, (size_t)nbytes); return 0; }, -1);
+}
+int gdbamd_importer_import_batch(void* h, uint8_t** cells, uint64_t* nbytes, int64_t* exhausted_pairs, int64_t* n_exhausted) {
+  return guarded([&] {
+    GenomicsDBImporter& imp = importer_of(h);
+    if (cells && !nbytes) throw GenomicsDBConfigException("gdbamd_importer_import_batch: cells without nbytes");
+    if (!exhausted_pairs || !n_exhausted) throw GenomicsDBConfigException("gdbamd_importer_import_batch: null exhausted arrays");
+    imp.import_batch();
+    const std::vector<uint8_t>& out = imp.last_batch_cells();
+    if (cells) {
+      *cells = (uint8_t*)malloc(out.size() ? out.size() : 1);
+      if (!*cells) throw GenomicsDBConfigException("out of memory");
+      if (!out.empty()) memcpy(*cells, out.data(), out.size());
+    }
+    if (nbytes) *nbytes = out.size();
+    const std::vector<BufferStreamIdentifier>& ex = imp.get_exhausted_buffer_stream_identifiers();
+    for (size_t i = 0; i < ex.size(); ++i) { exhausted_pairs[2 * i] = ex[i].first; exhausted_pairs[2 * i + 1] = (int64_t)ex[i].second; }
+    *n_exhausted = (int64_t)ex.size();
+    return 0;
+  }, -1);
+}
+int gdbamd_importer_is_done(void* h) { return guarded([&] { return importer_of(h).is_done() ? 1 : 0; }, -1); }
+int gdbamd_importer_finish(void* h) { return guarded([&] { importer_of(h).finish(); return 0; }, -1); }
+int gdbamd_importer_stats(void* h, double* stats) {
+  return guarded([&] {
+    if (!stats) throw GenomicsDBConfigException("gdbamd_importer_stats: null stats");
+    const StreamImportStats& st = importer_of(h).stats();
+    const double v[GDBAMD_IMPORTER_NUM_STATS] = {(double)st.num_batches, (double)st.num_records, (double)st.num_cells, (double)st.num_bytes, (double)st.max_pending_cells,
+                                                 (double)st.max_pending_bytes, (double)st.num_deferred_values, (double)st.num_spanning_cells, st.ms_order, st.ms_classify,
+                                                 st.ms_sort_gather, st.ms_compact, st.s_h2d, st.s_d2h};
+    memcpy(stats, v, sizeof(v));
+    return 0;
+  }, -1);
+}
+void gdbamd_importer_destroy(void* h) { delete static_cast<GenomicsDBImporter*>(h); }
+int gdbamd_chromosome_intervals_for_column_partition(const char* loader_json, int rank, char** json) {
+  return guarded([&] {
+    if (!loader_json || !json) throw GenomicsDBConfigException("gdbamd_chromosome_intervals_for_column_partition: null argument");
+    const std::string text = chromosome_intervals_for_column_partition(loader_json, rank);
+    *json = (char*)malloc(text.size() + 1);
+    if (!*json) throw GenomicsDBConfigException("out of memory");
+    memcpy(*json, text.c_str(), text.size() + 1);
+    return 0;
+  }, -1);
 }
 void gdbamd_free(void* p) { free(p); }
 

@@ -257,7 +257,11 @@ void VidMapper::parse_callsets_json(const mini_json::Value& doc) {
     CallSetInfo ci;
     ci.m_name = name; ci.m_row_idx = row;
     if (d.HasMember("idx_in_file")) ci.m_idx_in_file = d["idx_in_file"].GetInt64();
+    // a buffer stream is a source like a file: its name is matched where a "filename" is (reference vid_mapper.cc:996-1004)
+    if (d.HasMember("filename") && d.HasMember("stream_name"))
+      throw VidMapperException("Cannot have both \"filename\" and \"stream_name\" as the data source for sample/CallSet " + name);
     if (d.HasMember("filename")) ci.m_filename = d["filename"].GetString();
+    else if (d.HasMember("stream_name")) ci.m_filename = d["stream_name"].GetString();
     m_callsets.push_back(ci);
   }
   const mini_json::Value& lists = doc.HasMember("callsets") ? doc : doc["callset_mapping"];

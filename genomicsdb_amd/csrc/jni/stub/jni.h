@@ -4,8 +4,9 @@
  * source only.  It is NOT a general JNI header: only the types and the JNIEnv members the glue uses are declared.  What makes
  * the result loadable by a real JVM is the layout rule of the JNI specification ("JNI Functions", Interface Function Table):
  * JNIEnv points to a table of function pointers at FIXED indices - FindClass 6, ThrowNew 14, GetStringUTFChars 169,
- * ReleaseStringUTFChars 170, GetArrayLength 171, SetByteArrayRegion 208, ExceptionCheck 228 - and the wrappers below call
- * through exactly those slots.  genomicsdb_amd/build.py prefers $JAVA_HOME/include/jni.h whenever a JDK is present.
+ * ReleaseStringUTFChars 170, GetArrayLength 171, SetByteArrayRegion 208, ExceptionCheck 228, and for the importer glue
+ * (csrc/jni/jni_importer.cc) NewStringUTF 167, GetByteArrayElements 184, GetLongArrayElements 188, ReleaseByteArrayElements 192,
+ * ReleaseLongArrayElements 196 - and the wrappers below call through exactly those slots.  genomicsdb_amd/build.py prefers $JAVA_HOME/include/jni.h whenever a JDK is present.
  */
 #ifndef GDBAMD_STUB_JNI_H
 #define GDBAMD_STUB_JNI_H
@@ -36,12 +37,14 @@ class _jstring : public _jobject {};
 class _jthrowable : public _jobject {};
 class _jarray : public _jobject {};
 class _jbyteArray : public _jarray {};
+class _jlongArray : public _jarray {};
 typedef _jobject* jobject;
 typedef _jclass* jclass;
 typedef _jstring* jstring;
 typedef _jthrowable* jthrowable;
 typedef _jarray* jarray;
 typedef _jbyteArray* jbyteArray;
+typedef _jlongArray* jlongArray;
 
 struct JNIEnv_;
 typedef JNIEnv_ JNIEnv;
@@ -54,6 +57,11 @@ struct JNIEnv_ {
   jint ThrowNew(jclass cls, const char* msg) { return ((jint(*)(JNIEnv*, jclass, const char*))functions->slot[14])(this, cls, msg); }
   const char* GetStringUTFChars(jstring s, jboolean* is_copy) { return ((const char* (*)(JNIEnv*, jstring, jboolean*))functions->slot[169])(this, s, is_copy); }
   void ReleaseStringUTFChars(jstring s, const char* chars) { ((void (*)(JNIEnv*, jstring, const char*))functions->slot[170])(this, s, chars); }
+  jstring NewStringUTF(const char* utf) { return ((jstring(*)(JNIEnv*, const char*))functions->slot[167])(this, utf); }
+  jbyte* GetByteArrayElements(jbyteArray a, jboolean* is_copy) { return ((jbyte* (*)(JNIEnv*, jbyteArray, jboolean*))functions->slot[184])(this, a, is_copy); }
+  jlong* GetLongArrayElements(jlongArray a, jboolean* is_copy) { return ((jlong* (*)(JNIEnv*, jlongArray, jboolean*))functions->slot[188])(this, a, is_copy); }
+  void ReleaseByteArrayElements(jbyteArray a, jbyte* elems, jint mode) { ((void (*)(JNIEnv*, jbyteArray, jbyte*, jint))functions->slot[192])(this, a, elems, mode); }
+  void ReleaseLongArrayElements(jlongArray a, jlong* elems, jint mode) { ((void (*)(JNIEnv*, jlongArray, jlong*, jint))functions->slot[196])(this, a, elems, mode); }
   jsize GetArrayLength(jarray a) { return ((jsize(*)(JNIEnv*, jarray))functions->slot[171])(this, a); }
   void SetByteArrayRegion(jbyteArray a, jsize start, jsize len, const jbyte* buf) {
     ((void (*)(JNIEnv*, jbyteArray, jsize, jsize, const jbyte*))functions->slot[208])(this, a, start, len, buf);

@@ -64,6 +64,7 @@ class DeviceImporter {
   void finish(std::vector<uint8_t>& cells);
   const ImportStats& stats() const;
  private:
+  friend class DeviceStreamImporter;      // kernels/gdb_import_stream.h: the same batches, emitted batch by batch
   struct Impl;
   Impl* m_;
 };

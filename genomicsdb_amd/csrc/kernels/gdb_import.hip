@@ -52,6 +52,7 @@
 #include "../host/import_bcf.hpp"
 #include "../host/import_common.hpp"
 #include "gdb_import_device.hpp"
+#include "gdb_import_impl.hpp"
 #include "gdb_inflate.h"
 #include "gdb_pipeline.h"
 
@@ -319,84 +320,15 @@ __global__ void __launch_bounds__(kBlock) k_imp_gather(const uint32_t* idx, cons
 
 }  // namespace
 
-struct DeviceImporter::Impl {
-  int device = 0;
-  ImportOptions opt;
-  uint64_t budget = 0;
-  ImportTablesHost H;
-  std::vector<ImportFile> files;
-  std::vector<std::string> skipped_files;      // "filename"s whose callsets all lie outside the row bounds: never opened
-  ImportStats st;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  // tables, uploaded once
-  DBuf<char> d_names; DBuf<ImpName> d_contigs, d_fields; DBuf<ImpAttr> d_info, d_fmt;
-  DBuf<unsigned long long> d_row_best, d_counters;
-  DBuf<uint32_t> d_err, d_ndef;
-  bool spanning = false; int seq_bits = 64; uint64_t line_seq = 0;
-  bool spanning_slots = false;       // a batch whose slots take part in the partition-begin rule was queued (never a CSV batch)
-  ImportTextTap tap; bool tapped = false;      // tapped: text batches go to tap.on_batch once indexed, no cell is made
-  bool stage_in_lds = true;          // the A/B of profiles/device_import.md: -7.5 % on the write kernel; GDBAMD_IMPORT_STAGE_LDS=0|1 overrides
-  // per batch, reused
-  DBuf<char> d_text, d_tmp;
-  DBuf<uint64_t> d_tile, d_tile_scan, d_size, d_off, d_patch_at;
-  DBuf<uint32_t> d_nl, d_first_tab, d_tab, d_patch_val;
-  DBuf<int64_t> d_col, d_end, d_samp_row;
-  DBuf<int32_t> d_samp_idx;
-  DBuf<uint8_t> d_kind;
-  DBuf<ImpDeferred> d_def;
-  // what stays until finish()
-  struct Batch { uint64_t n_slots = 0, cells_bytes = 0; uint64_t* key = nullptr; uint64_t* src = nullptr; uint32_t* size = nullptr; uint64_t* tag = nullptr; uint8_t* cells = nullptr; };
-  std::vector<Batch> batches;
-  uint64_t total_slots = 0, total_cells = 0;
-  bool finished = false;
-  // BGZF input
-  int inflate_mode = DeviceImporter::kInflateAuto;
-  BgzfDeviceInflater inflater;
-  DBuf<char> d_win[2];               // the window and the one the carried partial line moves to
-  DBuf<unsigned long long> d_find;
-  // BCF2 input: the file's tables, and per batch the record offsets and the index pass's tables
-  DBuf<int32_t> d_dict_info, d_dict_fmt, d_dict_filter;
-  DBuf<int64_t> d_contig_off;
-  DBuf<uint32_t> d_rec_off;
-  DBuf<ImpBcfRec> d_rec;
-  DBuf<ImpBcfField> d_fld;
-
-  ImpTables tables(int n_samples) const {
-    ImpTables T = H.view(opt, n_samples);
-    T.names = d_names.p; T.contigs = d_contigs.p; T.fields = d_fields.p; T.info = d_info.p; T.fmt = d_fmt.p;
-    return T;
-  }
-  template <class T> void scan(const T* in, T* out, size_t n) {
-    size_t bytes = 0;
-    IMP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), n, rocprim::plus<T>(), stream));
-    d_tmp.ensure(std::max<size_t>(bytes, 16));
-    IMP_HIP_CHECK(rocprim::exclusive_scan((void*)d_tmp.p, bytes, in, out, T(0), n, rocprim::plus<T>(), stream));
-  }
-  void free_batches() {
-    for (Batch& b : batches) { if (b.key) (void)hipFree(b.key); if (b.src) (void)hipFree(b.src); if (b.size) (void)hipFree(b.size); if (b.tag) (void)hipFree(b.tag); if (b.cells) (void)hipFree(b.cells); }
-    batches.clear();
-  }
-  // text: host text to upload, or null when the batch is already in d_text; -> lines of the batch
-  // n_csv_rows >= 0: the lines are those of a CSV cell file, and d_samp_row holds that many rows of the file, ascending
-  uint32_t batch(const ImportFile& file, const ImportHeader& hdr, const char* text, size_t n, bool add_newline, int64_t lines_before, int n_imp, int n_csv_rows = -1);
-  int upload_samples(const ImportHeader& hdr);                              // -> imported samples of the file
-  void append_vcf_path(const ImportFile& file, double t0);                  // a file of VCF text: BGZF to the device as it is, else inflated here
-  void append_text(const ImportFile& file, const std::string& text);        // inflated text of a whole file, on the host
-  void append_bgzf(const ImportFile& file, const std::string& raw, const std::vector<BgzfMember>& mem);
-  void append_bcf(const ImportFile& file, const char* data, size_t n);      // a whole BCF2 stream, inflated
-  void append_csv(const ImportFile& file, const char* data, size_t n);      // a whole CSV cell file
-  const ImportFile& file_named(const std::string& filename) const;
-  // measure, layout and write of the n_lines x max(n_imp, 1) slots of a batch whose index pass is queued (ev[0], ev[1] recorded).
-  // host_text: the batch's text for the deferred tokens; describe(bit, line) / where(line): the words of an error
-  struct BatchWords {
-    std::function<const char*()> host_text; size_t n_text = 0;
-    std::function<std::string(uint32_t, uint32_t)> describe;
-    std::function<std::string(uint32_t)> where;
-  };
-  template <class Src> void cells_of_batch(const Src& src, const ImpTables& T, uint32_t n_lines, int n_imp, const BatchWords& words);
-  void find_newlines(const char* text, uint64_t lo, uint64_t mid, uint64_t hi, uint64_t* last_below, uint64_t* first_above);
-};
+namespace impdev {
+void launch_iota(uint32_t* v, uint64_t n, hipStream_t s) { if (n) hipLaunchKernelGGL(k_imp_iota, dim3(grid_for(n)), dim3(kBlock), 0, s, v, n); }
+void launch_sorted_sizes(const uint32_t* idx, const uint32_t* size, uint64_t kept, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_imp_sorted_sizes, dim3(grid_for(kept + 1)), dim3(kBlock), 0, s, idx, size, kept, out);
+}
+void launch_gather(const uint32_t* idx, const uint64_t* src, const uint32_t* size, const uint64_t* off, uint64_t kept, uint8_t* out, uint64_t out_bytes, hipStream_t s) {
+  if (kept) hipLaunchKernelGGL(k_imp_gather, dim3(grid_for(kept * 64)), dim3(kBlock), 0, s, idx, src, size, off, kept, out, out_bytes);
+}
+}  // namespace impdev
 
 DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes, int inflate_mode, const ImportTextTap* tap)
     : m_(new Impl) {
@@ -811,7 +743,7 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   words.where = [&](uint32_t line) { return file.path + " line " + std::to_string(lines_before + (int64_t)line + 1); };
   if (n_csv_rows >= 0) {
     words.describe = [&](uint32_t bit, uint32_t line) { return describe_csv_error(bit, words.where(line)); };
-    cells_of_batch(ImpCsvSrc{ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}, ImpCsvRows{d_samp_row.p, n_csv_rows}}, T, n_lines, n_imp, words);
+    cells_of_batch(ImpCsvSrc{ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}, ImpCsvRows{d_samp_row.p, n_csv_rows}}, T, n_lines, n_imp, words, true);
     return n_lines;
   }
   words.describe = [&](uint32_t bit, uint32_t line) {
@@ -831,11 +763,11 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
     IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1])); st.ms_index += ms;
     return n_lines;
   }
-  cells_of_batch(ImpTextSrc{{}, ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}}, T, n_lines, n_imp, words);
+  cells_of_batch(ImpTextSrc{{}, ImpBatch{d_text.p, d_nl.p, d_first_tab.p, d_tab.p, n_lines}}, T, n_lines, n_imp, words, true);
   return n_lines;
 }
 
-template <class Src> void DeviceImporter::Impl::cells_of_batch(const Src& src, const ImpTables& T, uint32_t n_lines, int n_imp, const BatchWords& words) {
+template <class Src> void DeviceImporter::Impl::cells_of_batch(const Src& src, const ImpTables& T, uint32_t n_lines, int n_imp, const BatchWords& words, bool text) {
   // ---- measure
   if (spanning && seq_bits < 64 && ((line_seq + n_lines + 1) >> seq_bits) != 0)
     throw VCF2BinaryException("too many record lines for the partition-begin rule of the device importer at column_begin " + std::to_string(opt.column_begin));
@@ -930,11 +862,10 @@ template <class Src> void DeviceImporter::Impl::cells_of_batch(const Src& src, c
   total_cells += counters[1];
   total_slots += n_slots;
   line_seq += n_lines;
+  if (after_batch) after_batch(n_lines, (uint32_t)std::max(n_imp, 1), text);
 }
 
-void DeviceImporter::Impl::append_bcf(const ImportFile& file, const char* data, size_t n) {
-  const BcfHeaderHost hdr = parse_bcf_header(data, n, file, H);
-  const int n_imp = upload_samples(hdr.samples);
+ImpBcfTables DeviceImporter::Impl::upload_bcf_tables(const BcfHeaderHost& hdr) {
   auto up = [&](auto& buf, const auto& v) {
     buf.ensure(std::max<size_t>(v.size(), 1));
     if (!v.empty()) IMP_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, stream));
@@ -943,11 +874,23 @@ void DeviceImporter::Impl::append_bcf(const ImportFile& file, const char* data, 
   IMP_HIP_CHECK(hipStreamSynchronize(stream));
   ImpBcfTables BT = hdr.view();
   BT.dict_info = d_dict_info.p; BT.dict_fmt = d_dict_fmt.p; BT.dict_filter = d_dict_filter.p; BT.contig_off = d_contig_off.p;
-  const ImpTables T = tables(hdr.samples.n_samples);
-  const uint32_t n_attr = (uint32_t)(H.info.size() + H.fmt.size());
+  return BT;
+}
+
+void DeviceImporter::Impl::append_bcf(const ImportFile& file, const char* data, size_t n) {
+  const BcfHeaderHost hdr = parse_bcf_header(data, n, file, H);
+  const int n_imp = upload_samples(hdr.samples);
+  const ImpBcfTables BT = upload_bcf_tables(hdr);
   // the host walks the chain (8 bytes per record) and cuts batches at record boundaries
   std::vector<uint64_t> offs;
   bcf_walk_records(data, n, hdr.records_begin, file.path, offs);
+  bcf_batches(file, hdr, BT, n_imp, data, offs, 0);
+}
+
+void DeviceImporter::Impl::bcf_batches(const ImportFile& file, const BcfHeaderHost& hdr, const ImpBcfTables& BT, int n_imp, const char* data,
+                                       const std::vector<uint64_t>& offs, uint64_t records_before) {
+  const ImpTables T = tables(hdr.samples.n_samples);
+  const uint32_t n_attr = (uint32_t)(H.info.size() + H.fmt.size());
   std::vector<uint32_t> rel;
   for (size_t first = 0; first + 1 < offs.size();) {
     const size_t last = bcf_next_batch(offs, first, budget);
@@ -975,11 +918,11 @@ void DeviceImporter::Impl::append_bcf(const ImportFile& file, const char* data, 
     IMP_HIP_CHECK(hipEventRecord(ev[1], stream));
     BatchWords words;
     words.host_text = []() -> const char* { return nullptr; };      // (nothing is deferred)
-    words.where = [&](uint32_t r) { return file.path + " record " + std::to_string(first + r + 1); };
+    words.where = [&](uint32_t r) { return file.path + " record " + std::to_string(records_before + first + r + 1); };
     words.describe = [&](uint32_t bit, uint32_t r) {
       return describe_bcf_error(bit, H, opt, hdr, (const uint8_t*)data + base, rel[r], rel[r + 1u], words.where(r));
     };
-    cells_of_batch(ImpBcfSrc{{}, BT, (const uint8_t*)d_text.p, d_rec.p, d_fld.p, n_attr}, T, n_rec, n_imp, words);
+    cells_of_batch(ImpBcfSrc{{}, BT, (const uint8_t*)d_text.p, d_rec.p, d_fld.p, n_attr}, T, n_rec, n_imp, words, false);
     first = last;
   }
 }

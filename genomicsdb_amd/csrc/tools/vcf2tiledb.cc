@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../api/genomicsdb_bcf_generator.h"
+#include "../api/loader_outputs.h"
 #include "../common/mini_json.hpp"
 #include "../host/vcf_importer.h"
 #include "../kernels/gdb_split.h"
@@ -45,11 +46,6 @@ static int launcher_rank() {
     if (const char* e = getenv(name)) return atoi(e);
   return 0;
 }
-static void mkdir_p(const std::string& path) {
-  for (size_t i = 1; i <= path.size(); ++i)
-    if (i == path.size() || path[i] == '/') mkdir(path.substr(0, i).c_str(), 0755);
-}
-
 static void write_text_file(const std::string& path, const std::string& text, const char* what) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) throw GenomicsDBConfigException(std::string("Could not write to partitioned ") + what + " JSON file " + path);
@@ -190,86 +186,9 @@ int main(int argc, char** argv) {
     if (import_on_device)
       std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",vcf2binary_inflate,compressed_bytes," << st.compressed_bytes << ",device_members," << st.num_device_members
                 << ",host_inflated_files," << st.num_host_inflated_files << ",inflate_kernel_ms," << st.ms_inflate << "\n";
-    const bool produce_array = doc.HasMember("produce_tiledb_array") && doc["produce_tiledb_array"].GetBool();
-    if (produce_array) {
-      const std::string dir = loader.get_workspace(rank) + "/" + loader.get_array_name(rank);
-      mkdir_p(dir);
-      const std::string array_file = dir + "/cells.bin";
-      struct stat have;
-      const bool merge = loader.m_has_delete_and_create_tiledb_array && !loader.m_delete_and_create_tiledb_array && ::stat(array_file.c_str(), &have) == 0;
-      std::vector<uint8_t> merged;
-      if (merge) {      // the batch joins the cells the array holds: on the device, or not at all
-        const auto tm = std::chrono::steady_clock::now();
-        std::vector<uint8_t> old((size_t)have.st_size);
-        FILE* in = fopen(array_file.c_str(), "rb");
-        if (!in) throw GenomicsDBConfigException("cannot read " + array_file);
-        const size_t got = old.empty() ? 0 : fread(old.data(), 1, old.size(), in);
-        fclose(in);
-        if (got != old.size()) throw GenomicsDBConfigException("short read from " + array_file);
-        MergeStats ms;
-        std::vector<CellStream> streams(2);
-        streams[0].data = old.data(); streams[0].nbytes = old.size();
-        streams[1].data = cells.data(); streams[1].nbytes = cells.size();
-        merged = merge_cell_streams_device(streams, device, &ms);
-        std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",merge_tiledb_array,Wall-clock time(s)," << std::chrono::duration<double>(std::chrono::steady_clock::now() - tm).count()
-                  << ",streams," << ms.num_streams << ",cells_in," << ms.cells_in << ",cells_out," << ms.cells_out << ",bytes_out," << ms.bytes_out << ",tile," << ms.tile
-                  << ",keys_ms," << ms.ms_keys << ",rank_ms," << ms.ms_rank << ",scan_ms," << ms.ms_scan << ",gather_ms," << ms.ms_gather << ",h2d_s," << ms.s_h2d
-                  << ",d2h_s," << ms.s_d2h << ",merge_s," << ms.s_total << "\n";
-      }
-      const std::vector<uint8_t>& array_cells = merge ? merged : cells;
-      const std::string write_to = merge ? array_file + ".merge.tmp" : array_file;
-      FILE* f = fopen(write_to.c_str(), "wb");
-      if (!f) throw GenomicsDBConfigException("cannot write " + write_to);
-      if (!array_cells.empty() && fwrite(array_cells.data(), 1, array_cells.size(), f) != array_cells.size()) {
-        fclose(f);
-        if (merge) remove(write_to.c_str());
-        throw GenomicsDBConfigException("short write to " + write_to);
-      }
-      if (fclose(f) != 0) throw GenomicsDBConfigException("cannot write " + write_to);
-      if (merge && rename(write_to.c_str(), array_file.c_str()) != 0) { remove(write_to.c_str()); throw GenomicsDBConfigException("cannot rename " + write_to + " to " + array_file); }
-      remove((dir + "/fragment.gdbamd").c_str());   // a columnar copy of older cells must not shadow the new array
-      // "compress_tiledb_array" (the reference's loader gzips the attribute tiles of the array it writes): the columnar fragment file with
-      // its data sections as DEFLATE tiles goes next to cells.bin; queries read it window by window and inflate the tiles on the device
-      if (doc.HasMember("compress_tiledb_array") && doc["compress_tiledb_array"].GetBool() && !array_cells.empty()) {
-        const auto tc = std::chrono::steady_clock::now();
-        const size_t close_at = loader_text.rfind('}');
-        if (close_at == std::string::npos) throw GenomicsDBConfigException("loader JSON is not an object");
-        const std::string all_text = loader_text.substr(0, close_at) + ", \"query_column_ranges\": [[[" + std::to_string(part.first) + ", " + std::to_string(part.second) + "]]]" +
-                                     loader_text.substr(close_at);
-        try {
-          CombineEngine eng(mini_json::parse(all_text), 0, nullptr, rank, "", false);
-          eng.stage_cells(array_cells.data(), array_cells.size());
-          eng.save_fragment(dir + "/fragment.gdbamd", true);
-          struct stat fs;
-          const long long zbytes = ::stat((dir + "/fragment.gdbamd").c_str(), &fs) == 0 ? (long long)fs.st_size : -1;
-          std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",compress_tiledb_array,Wall-clock time(s)," << std::chrono::duration<double>(std::chrono::steady_clock::now() - tc).count()
-                    << ",cells_bytes," << array_cells.size() << ",fragment_bytes," << zbytes << "\n";
-        } catch (const GenomicsDBDeviceException& e) {
-          // (the columnar file is built from columns staged in HBM: without a device the array stays as cells.bin, which every reader accepts)
-          std::cerr << "vcf2tiledb: compress_tiledb_array skipped: " << e.what() << "\n";
-        }
-      }
-    }
-    if (loader.m_produce_combined_vcf) {
-      // the loader JSON doubles as the query JSON of the in-line combine: every attribute, the whole column partition
-      const size_t close = loader_text.rfind('}');
-      if (close == std::string::npos) throw GenomicsDBConfigException("loader JSON is not an object");
-      const std::string query_text = loader_text.substr(0, close) + ", \"query_column_ranges\": [[[" + std::to_string(part.first) + ", " + std::to_string(part.second) +
-                                     "]]]" + loader_text.substr(close);
-      const size_t capacity = (size_t)64u << 20;
-      GenomicsDBBCFGenerator gen(query_text, cells.data(), cells.size(), capacity, false);
-      std::vector<uint8_t> buf(capacity);
-      size_t total = 0;
-      while (!gen.end()) {
-        const size_t n = gen.read_and_advance(buf.data(), 0, buf.size());
-        if (n == 0) break;
-        if (fwrite(buf.data(), 1, n, stdout) != n) { std::cerr << "short write\n"; return -1; }
-        total += n;
-      }
-      fflush(stdout);
-      const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_import;
-      std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",produce_combined_vcf,Wall-clock time(s)," << secs << ",bytes," << total << "\n";
-    }
+    LoaderOutputs out;
+    out.loader_text = loader_text; out.rank = rank; out.device = device; out.tool = "vcf2tiledb";
+    produce_loader_outputs(out, doc, loader, &cells);
   } catch (const std::exception& e) {
     std::cerr << "vcf2tiledb: " << e.what() << "\n";
     return -1;

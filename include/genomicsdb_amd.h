@@ -342,6 +342,35 @@ int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nb
 int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
                               const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
                               uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs);
+/* The streaming importer (GenomicsDBImporter, csrc/api/genomicsdb_importer.h; kernels/gdb_import_stream.hip): buffer streams of VCF text or BCF2
+ * records imported batch by batch on one GPU with bounded device memory; INTEGRATION.md has the protocol.  loader_json: the path of a loader JSON, or
+ * the JSON itself (a string that begins with '{').  device < 0: GDBAMD_DEVICE, else LOCAL_RANK, else 0.  Every call but create and destroy returns 0
+ * on success and -1 on an error, whose text gdb_mi355_last_error has; create returns NULL on an error.
+ *   add_buffer_stream  before setup_loader only; init: the header (VCF text through the #CHROM line, or BCF\2\2 + l_text + text)
+ *   setup_loader       callsets_json: NULL / "" or {"callsets": ..} to join those of the loader's callset_mapping_file; *max_identifiers: the number of used streams
+ *   stream_file_idx    the stream's index among the sources of the callset mapping, -1: no callset inside the row bounds uses it
+ *   write              whole records; replaces the stream's buffer; partition_idx must be 0
+ *   import_batch       *cells (cells may be NULL: the cells are not wanted) is malloc'ed, release with gdbamd_free; exhausted_pairs: room for 2 * max_identifiers
+ *                      values, receives (stream, 0) pairs, *n_exhausted their number.  A reported stream is refilled, or ended by a write of 0 bytes or by no write
+ *   is_done            1 when every used stream has ended and nothing is pending, else 0
+ *   finish             only when done: the loader's outputs (produce_tiledb_array, produce_combined_vcf, ..)
+ *   stats              GDBAMD_IMPORTER_NUM_STATS doubles: 0 batches, 1 records, 2 cells and 3 bytes handed over, 4 max pending cells, 5 max pending bytes,
+ *                      6 deferred values, 7 cells replayed at the partition begin, 8..11 HIP-event ms of order check / classify / sort + gather / compact,
+ *                      12..13 wall seconds of H2D and D2H */
+#define GDBAMD_IMPORTER_NUM_STATS 14
+void* gdbamd_importer_create(const char* loader_json, int rank, int device);
+int gdbamd_importer_add_buffer_stream(void* importer, const char* name, int is_bcf, uint64_t capacity, const uint8_t* init, uint64_t init_nbytes);
+int gdbamd_importer_setup_loader(void* importer, const char* callsets_json, int64_t* max_identifiers);
+int gdbamd_importer_stream_file_idx(void* importer, int64_t stream_idx, int64_t* file_idx);
+int gdbamd_importer_write(void* importer, int64_t stream_idx, unsigned partition_idx, const uint8_t* data, uint64_t nbytes);
+int gdbamd_importer_import_batch(void* importer, uint8_t** cells, uint64_t* nbytes, int64_t* exhausted_pairs, int64_t* n_exhausted);
+int gdbamd_importer_is_done(void* importer);
+int gdbamd_importer_finish(void* importer);
+int gdbamd_importer_stats(void* importer, double* stats);
+void gdbamd_importer_destroy(void* importer);
+/* {"contigs":[{"<name>":[begin,end]},...]}: the 1-based chromosome intervals that column partition `rank` of the loader JSON covers (reference
+ * VidMapper::get_contig_intervals_for_column_partition, vid_mapper.cc:576-609).  *json is malloc'ed: release with gdbamd_free */
+int gdbamd_chromosome_intervals_for_column_partition(const char* loader_json, int rank, char** json);
 void gdbamd_free(void* p);
 
 #ifdef __cplusplus
