@@ -571,6 +571,54 @@ def split_files(vid_mapping_file, callset_mapping_file, partitions, results_dire
     return result
 
 
+HISTOGRAM_STAT_NAMES = tuple(name for name, _ in _lib.HistogramStats._fields_)
+
+
+def input_histogram(vid_mapping_file, callset_mapping_file, max_histogram_range, num_bins, file_root="", column_begin=0, column_end=2**63 - 2,
+                    lb_callset_row_idx=0, ub_callset_row_idx=2**63 - 2, device=0, text_budget_bytes=0, inflate="auto", streams=None, stats=None):
+    """vcf_histogram on GPU `device` (kernels/gdb_histogram.hip): one pass over every input file of the callset mapping ((g)VCF text -
+    plain, gzip or BGZF - and BCF2; `streams`, {filename: bytes}, gives files from memory as for import_cells) counts the records per
+    bin of a uniform histogram over the columns [0, max_histogram_range]: size_of_bin = ceil((max_histogram_range + 1) / num_bins),
+    bin = column // size_of_bin.  A record counts iff its column (contig offset + POS - 1) lies in [column_begin, column_end], once
+    per callset of its file whose row lies in the row bounds.  -> numpy uint64 array of num_bins counts.  CSV cell files are refused
+    by name; a counted column above max_histogram_range and a line the splitter would refuse raise an error that names file and
+    1-based line / record.  `stats`, a dict, receives HISTOGRAM_STAT_NAMES."""
+    import numpy as np
+    if inflate not in INFLATE_MODES:
+        raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
+    if int(num_bins) < 0:
+        raise ValueError("num_bins=%r is negative" % (num_bins,))
+    L = _lib.lib()
+    items = [(os.fsencode(k), bytes(v)) for k, v in (streams or {}).items()]
+    ns = len(items)
+    names = (ctypes.c_char_p * max(ns, 1))(*[k for k, _ in items])
+    data = (ctypes.c_void_p * max(ns, 1))(*[ctypes.cast(ctypes.c_char_p(v), ctypes.c_void_p) for _, v in items])      # (items keeps the bytes alive)
+    sizes = (ctypes.c_uint64 * max(ns, 1))(*[len(v) for _, v in items])
+    counts = np.zeros(max(int(num_bins), 1), dtype=np.uint64)
+    st = _lib.HistogramStats()
+    rc = L.gdbamd_input_histogram(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), int(max_histogram_range), int(num_bins),
+                                  int(column_begin), int(column_end), int(lb_callset_row_idx), int(ub_callset_row_idx), int(device), int(text_budget_bytes),
+                                  INFLATE_MODES[inflate], ns, names, data, sizes, counts.ctypes.data, ctypes.byref(st))
+    _check(rc == 0, "input_histogram")
+    if stats is not None:
+        stats.update({k: getattr(st, k) for k in HISTOGRAM_STAT_NAMES})
+    return counts
+
+
+def histogram_text(counts, max_histogram_range):
+    """Histogram::print of the reference for the counts of input_histogram: "Histogram: [", one "lo,hi,count" line per non-zero
+    bin, "]"; -> str"""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    L = _lib.lib()
+    n = L.gdbamd_histogram_text(counts.ctypes.data, counts.size, int(max_histogram_range), None, 0)
+    if n < 0:
+        raise ValueError("histogram_text: no bin, or a negative max_histogram_range")
+    buf = ctypes.create_string_buffer(n + 1)
+    L.gdbamd_histogram_text(counts.ctypes.data, counts.size, int(max_histogram_range), buf, n)
+    return buf.raw[:n].decode()
+
+
 MERGE_STAT_NAMES = ("num_streams", "cells_in", "cells_out", "bytes_out", "tile", "ms_keys", "ms_rank", "ms_scan", "ms_gather", "s_h2d", "s_d2h", "s_total")
 
 

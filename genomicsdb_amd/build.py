@@ -13,7 +13,8 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(PKG, "libgenomicsdb_amd.so")
 TOOL = os.path.join(PKG, "gt_mpi_gather")
-TOOLS = {"gt_mpi_gather": TOOL, "vcf2tiledb": os.path.join(PKG, "vcf2tiledb"), "test_genomicsdb_importer": os.path.join(PKG, "test_genomicsdb_importer")}
+TOOLS = {"gt_mpi_gather": TOOL, "vcf2tiledb": os.path.join(PKG, "vcf2tiledb"), "test_genomicsdb_importer": os.path.join(PKG, "test_genomicsdb_importer"),
+         "vcf_histogram": os.path.join(PKG, "vcf_histogram")}
 
 SOURCES = [
     "kernels/gdb_pipeline.hip",
@@ -23,6 +24,7 @@ SOURCES = [
     "kernels/gdb_inflate.hip",
     "kernels/gdb_merge.hip",
     "kernels/gdb_split.hip",
+    "kernels/gdb_histogram.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -173,6 +175,14 @@ def build_hostsim_split():
     d = os.path.join(ROOT, "tests", "hostsim_split")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "hostsim_split")
+
+
+def build_hostsim_histogram():
+    """The bodies of the input histogram (core/gdb_histogram.hpp) as a stand-alone program built with the address and
+    undefined-behaviour sanitizers (tests only); -> program"""
+    d = os.path.join(ROOT, "tests", "hostsim_histogram")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "hostsim_histogram")
 
 
 def build_hostsim_inflate():

@@ -12,6 +12,7 @@
 #include "../kernels/gdb_import_stream.h"
 #include "../kernels/gdb_bgzf.h"
 #include "../kernels/gdb_inflate.h"
+#include "../kernels/gdb_histogram.h"
 #include "../kernels/gdb_split.h"
 #include "../host/vcf_importer.h"
 #include "../host/vcf_index.h"
@@ -581,6 +582,47 @@ int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_
     g_last_error.clear();
     return 0;
   } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int gdbamd_input_histogram(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int64_t max_histogram_range, uint64_t num_bins,
+                           int64_t column_begin, int64_t column_end, int64_t lb_callset_row_idx, int64_t ub_callset_row_idx, int device,
+                           uint64_t text_budget_bytes, int inflate_mode, int nstreams, const char* const* names, const void* const* data,
+                           const uint64_t* stream_nbytes, uint64_t* counts, gdbamd_histogram_stats* stats) {
+  try {
+    if (!vid_mapping_file || !callset_mapping_file || !counts) throw GenomicsDBConfigException("gdbamd_input_histogram: null argument");
+    if (nstreams < 0 || (nstreams > 0 && (!names || !data || !stream_nbytes))) throw GenomicsDBConfigException("gdbamd_input_histogram: null stream arrays");
+    InputHistogramRequest req;
+    for (int i = 0; i < nstreams; ++i) {
+      if (!names[i]) throw GenomicsDBConfigException("gdbamd_input_histogram: null stream name");
+      ImportStream s;
+      s.name = names[i]; s.data = data[i]; s.nbytes = stream_nbytes[i];
+      req.streams.push_back(s);
+    }
+    VidMapper vid;
+    vid.parse_vid_json(mini_json::parse_file(vid_mapping_file));
+    vid.parse_callsets_json(mini_json::parse_file(callset_mapping_file));
+    req.max_histogram_range = max_histogram_range; req.num_bins = num_bins;
+    req.column_begin = column_begin; req.column_end = column_end;
+    req.row_begin = lb_callset_row_idx; req.row_end = ub_callset_row_idx;
+    if (file_root) req.file_root = file_root;
+    req.device = device; req.text_budget_bytes = text_budget_bytes; req.inflate_mode = inflate_mode;
+    InputHistogramStats st;
+    const std::vector<uint64_t> out = input_histogram_device(vid, req, &st);
+    memcpy(counts, out.data(), out.size() * sizeof(uint64_t));
+    if (stats) {
+      stats->num_files = st.num_files; stats->num_records = st.num_records; stats->num_counted = st.num_counted; stats->total_weight = st.total_weight;
+      stats->num_batches = st.num_batches; stats->num_atomics = st.num_atomics;
+      stats->ms_index = st.ms_index; stats->ms_inflate = st.ms_inflate; stats->ms_histogram = st.ms_histogram;
+      stats->s_read = st.s_read; stats->s_h2d = st.s_h2d; stats->s_total = st.s_total;
+    }
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int64_t gdbamd_histogram_text(const uint64_t* counts, uint64_t num_bins, int64_t max_histogram_range, char* dst, uint64_t cap) {
+  if (!counts || num_bins == 0 || max_histogram_range < 0) return -1;
+  const std::string out = histogram_text(counts, num_bins, (uint64_t)max_histogram_range);
+  if (dst && cap) { const size_t n = std::min<size_t>(out.size(), (size_t)cap); memcpy(dst, out.data(), n); }
+  return (int64_t)out.size();
 }
 // ---- the streaming importer (api/genomicsdb_importer.h)
 void* gdbamd_importer_create(const char* loader_json, int rank, int device) {

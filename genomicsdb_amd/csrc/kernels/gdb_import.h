@@ -21,9 +21,9 @@
 
 namespace genomicsdb_amd {
 
-namespace gdbimp { struct ImpTables; }      // core/gdb_import.hpp
+namespace gdbimp { struct ImpTables; struct ImpBcfTables; }      // core/gdb_import.hpp, core/gdb_import_bcf.hpp
 
-// A text tap takes the importer's batches in place of the cells (kernels/gdb_split.hip): the same files, windows, batch cuts and
+// A text tap takes the importer's batches in place of the cells (kernels/gdb_split.hip, kernels/gdb_histogram.hip): the same files, windows, batch cuts and
 // newline / tab index, then on_batch instead of measure and write.  Every pointer of a batch is device memory that is valid until
 // on_batch returns; the index is queued on `stream` (a hipStream_t), on which on_batch queues its own work.
 struct ImportTextBatch {
@@ -36,9 +36,21 @@ struct ImportTextBatch {
   void* stream;
   std::function<std::string(uint32_t bit, uint32_t line)> describe;      // the words of an ImpErr bit raised on a line of the batch
 };
+// The same for a batch of BCF2 records (kernels/gdb_histogram.hip): the bytes as the host's walk of the l_shared / l_indiv chain cut
+// them, record r in [d_rec_off[r], d_rec_off[r + 1]); then on_records instead of the index pass, measure and write.
+struct ImportRecordBatch {
+  const std::string* path;                      // the file or stream, for messages
+  const uint8_t* d_bytes; const uint32_t* d_rec_off;      // n_bytes of whole records; n_rec + 1 offsets
+  uint32_t n_bytes, n_rec;
+  int64_t records_before;                       // records of the file in front of the batch
+  const gdbimp::ImpBcfTables* bcf_tables;       // the header's dictionaries against the vid, in device memory (the struct itself is the host's)
+  void* stream;
+  std::function<std::string(uint32_t bit, uint32_t rec)> describe;       // the words of an error bit raised on a record of the batch
+};
 struct ImportTextTap {
   std::function<void(const std::string& path, const std::string& head)> on_header;      // a file's lines in front of its first record line
   std::function<void(const ImportTextBatch&)> on_batch;
+  std::function<void(const ImportRecordBatch&)> on_records;      // unset: BCF2 input is refused by name
 };
 
 class DeviceImporter {

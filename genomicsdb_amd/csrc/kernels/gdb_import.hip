@@ -911,6 +911,20 @@ void DeviceImporter::Impl::bcf_batches(const ImportFile& file, const BcfHeaderHo
     IMP_HIP_CHECK(hipStreamSynchronize(stream));
     st.bytes_h2d += n_bytes + rel.size() * sizeof(uint32_t);
     st.s_h2d += now_s() - t0;
+    if (tapped) {       // the uploaded batch is the product
+      if (!tap.on_records) throw VCF2BinaryException(file.path + " is BCF2: this tap takes (g)VCF text only");
+      ImportRecordBatch b;
+      b.path = &file.path; b.d_bytes = (const uint8_t*)d_text.p; b.d_rec_off = d_rec_off.p; b.n_bytes = (uint32_t)n_bytes; b.n_rec = n_rec;
+      b.records_before = (int64_t)(records_before + first); b.bcf_tables = &BT; b.stream = (void*)stream;
+      b.describe = [&](uint32_t bit, uint32_t r) {
+        return describe_bcf_error(bit, H, opt, hdr, (const uint8_t*)data + base, rel[r], rel[r + 1u],
+                                  file.path + " record " + std::to_string(records_before + first + r + 1));
+      };
+      tap.on_records(b);
+      IMP_HIP_CHECK(hipStreamSynchronize(stream));
+      first = last;
+      continue;
+    }
     // ---- index: one thread per record
     IMP_HIP_CHECK(hipEventRecord(ev[0], stream));
     hipLaunchKernelGGL(k_imp_bcf_index, dim3(grid_for(n_rec)), dim3(kBlock), 0, stream, T, BT, (const uint8_t*)d_text.p, (uint32_t)n_bytes, (const uint32_t*)d_rec_off.p, n_rec,

@@ -342,6 +342,29 @@ int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nb
 int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
                               const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
                               uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs);
+/* vcf_histogram on GPU `device` (kernels/gdb_histogram.hip; reference tools/src/vcf_histogram.cc, tiledb_loader.cc:428-456, utils/histogram.cc): one pass
+ * over every input file of the callset mapping - (g)VCF text, plain, gzip or BGZF, and BCF2; a file whose name is one of the nstreams `names` is read from
+ * memory - counts its records per bin of a uniform histogram over the columns [0, max_histogram_range]:
+ *   size_of_bin = (max_histogram_range + 1 + (num_bins - 1)) / num_bins,  bin = column / size_of_bin,  column = contig offset + POS - 1.
+ * A record counts iff its column lies in [column_begin, column_end], and it counts once per callset of its file whose row lies in
+ * [lb_callset_row_idx, ub_callset_row_idx]; a file without such a callset is not opened.  counts: num_bins values, filled on success only.
+ * Refused before anything runs: num_bins == 0, a negative max_histogram_range, counters that do not fit in device memory, CSV cell files (by name).
+ * Errors that name file and 1-based line / record: a counted column above max_histogram_range, a contig that is not in the vid, POS / END that is no plain
+ * integer, fewer than 8 columns.  text_budget_bytes and inflate_mode as for gdbamd_import_cells_device_ex.  stats may be NULL. */
+typedef struct gdbamd_histogram_stats {
+  int64_t num_files, num_records, num_counted;  /* files read; record lines / records seen; those inside the column bounds */
+  uint64_t total_weight;                        /* the sum of all bins */
+  int64_t num_batches, num_atomics;             /* batches; atomic adds on the counters (one per run of equal bins inside a wavefront) */
+  double ms_index, ms_inflate, ms_histogram;    /* HIP-event ms of the index pass, the BGZF inflate kernel and the histogram kernel, summed over the batches */
+  double s_read, s_h2d, s_total;                /* wall seconds of file read (+ host inflate), uploads, the whole call */
+} gdbamd_histogram_stats;
+int gdbamd_input_histogram(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int64_t max_histogram_range, uint64_t num_bins,
+                           int64_t column_begin, int64_t column_end, int64_t lb_callset_row_idx, int64_t ub_callset_row_idx, int device,
+                           uint64_t text_budget_bytes, int inflate_mode, int nstreams, const char* const* names, const void* const* data,
+                           const uint64_t* stream_nbytes, uint64_t* counts, gdbamd_histogram_stats* stats);
+/* Histogram::print of the reference: "Histogram: [\n", then "lo,hi,count\n" for every non-zero bin (lo = b * size_of_bin, hi = (b + 1) * size_of_bin - 1), then
+ * "]\n".  Returns the length of the text (dst may be NULL: call once to measure, once to write), -1 when num_bins is 0 or max_histogram_range negative */
+int64_t gdbamd_histogram_text(const uint64_t* counts, uint64_t num_bins, int64_t max_histogram_range, char* dst, uint64_t cap);
 /* The streaming importer (GenomicsDBImporter, csrc/api/genomicsdb_importer.h; kernels/gdb_import_stream.hip): buffer streams of VCF text or BCF2
  * records imported batch by batch on one GPU with bounded device memory; INTEGRATION.md has the protocol.  loader_json: the path of a loader JSON, or
  * the JSON itself (a string that begins with '{').  device < 0: GDBAMD_DEVICE, else LOCAL_RANK, else 0.  Every call but create and destroy returns 0
