@@ -51,7 +51,7 @@ SYMBOLS = ["gdb_mi355_last_error", "gdb_mi355_device_count", "gdb_mi355_init", "
            "gdbamd_engine_column_histogram", "gdbamd_equi_partition_text", "gdbamd_build_output_index", "gdbamd_engine_print_calls", "gdbamd_engine_print_cells", "gdbamd_engine_query_variants", "gdbamd_pin_host_memory", "gdbamd_unpin_host_memory",
            "gdbamd_importer_create", "gdbamd_importer_add_buffer_stream", "gdbamd_importer_setup_loader", "gdbamd_importer_stream_file_idx", "gdbamd_importer_write",
            "gdbamd_importer_import_batch", "gdbamd_importer_is_done", "gdbamd_importer_finish", "gdbamd_importer_stats", "gdbamd_importer_destroy",
-           "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text"]
+           "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text", "gdbamd_vcfdiff"]
 
 
 class HistogramStats(ctypes.Structure):
@@ -59,6 +59,14 @@ class HistogramStats(ctypes.Structure):
     _fields_ = [("num_files", ctypes.c_int64), ("num_records", ctypes.c_int64), ("num_counted", ctypes.c_int64), ("total_weight", ctypes.c_uint64),
                 ("num_batches", ctypes.c_int64), ("num_atomics", ctypes.c_int64), ("ms_index", ctypes.c_double), ("ms_inflate", ctypes.c_double),
                 ("ms_histogram", ctypes.c_double), ("s_read", ctypes.c_double), ("s_h2d", ctypes.c_double), ("s_total", ctypes.c_double)]
+
+
+class VcfDiffStats(ctypes.Structure):
+    """gdbamd_vcfdiff_stats of include/genomicsdb_amd.h"""
+    _fields_ = [("gold_records", ctypes.c_int64), ("test_records", ctypes.c_int64), ("pairs_compared", ctypes.c_int64), ("pairs_light", ctypes.c_int64),
+                ("pairs_heavy", ctypes.c_int64), ("deferred", ctypes.c_int64), ("events", ctypes.c_int64), ("num_batches", ctypes.c_int64),
+                ("resident_bytes", ctypes.c_uint64), ("ms_index", ctypes.c_double), ("ms_inflate", ctypes.c_double), ("ms_keys", ctypes.c_double),
+                ("ms_compare", ctypes.c_double), ("s_read", ctypes.c_double), ("s_walk", ctypes.c_double), ("s_total", ctypes.c_double)]
 
 
 def lib():
@@ -157,6 +165,7 @@ def lib():
                                             c.c_uint64, c.c_int, c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_double), c.c_int, c.POINTER(c.c_void_p)]
     L.gdbamd_input_histogram.argtypes = [c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_uint64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int, c.c_uint64, c.c_int,
                                          c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_void_p), c.POINTER(c.c_uint64), c.c_void_p, c.POINTER(HistogramStats)]
+    L.gdbamd_vcfdiff.argtypes = [c.c_char_p, c.c_char_p, c.c_double, c.c_char_p, c.c_int, c.c_uint64, c.POINTER(c.c_void_p), c.POINTER(VcfDiffStats)]
     L.gdbamd_histogram_text.restype = c.c_int64
     L.gdbamd_histogram_text.argtypes = [c.c_void_p, c.c_uint64, c.c_int64, c.c_char_p, c.c_uint64]
     L.gdbamd_bgzf_decompress.argtypes = [c.c_char_p, c.c_uint64, c.c_char_p, c.c_uint64, c.POINTER(c.c_uint64), c.POINTER(c.c_float), c.c_int]

@@ -619,6 +619,32 @@ def histogram_text(counts, max_histogram_range):
     return buf.raw[:n].decode()
 
 
+VCFDIFF_STAT_NAMES = tuple(name for name, _ in _lib.VcfDiffStats._fields_)
+
+
+def vcfdiff(gold, test, threshold=1e-5, regions="", device=0, text_budget_bytes=0, stats=None):
+    """vcfdiff on GPU `device` (kernels/gdb_vcfdiff.hip): the VCF text files `gold` and `test` (plain, gzip or BGZF) compared record by
+    record, the order of ALT alleles (AD / PL / AF and the like are compared through the allele permutation), of INFO keys, FORMAT keys
+    and sample columns and float noise below `threshold` aside; DESIGN.md, "Comparing two VCFs", has the rule.  regions: chr | chr:pos |
+    chr:from-to | chr:from- , comma separated.  -> {"compared": pairs compared, "events": [...]}: in order, every event that is not a
+    clean COMPARED pair, with its kind, the 1-based line numbers, the lines, the flag names and the field names per mask.  BCF2 input,
+    differing sample names and more than 64 INFO or FORMAT names are refused; a line error names file and 1-based line.  `stats`, a
+    dict, receives VCFDIFF_STAT_NAMES."""
+    import json
+    L = _lib.lib()
+    p = ctypes.c_void_p()
+    st = _lib.VcfDiffStats()
+    rc = L.gdbamd_vcfdiff(os.fsencode(gold), os.fsencode(test), float(threshold), os.fsencode(regions or ""), int(device), int(text_budget_bytes), ctypes.byref(p),
+                          ctypes.byref(st))
+    _check(rc == 0, "vcfdiff")
+    if stats is not None:
+        stats.update({k: getattr(st, k) for k in VCFDIFF_STAT_NAMES})
+    try:
+        return json.loads(ctypes.string_at(p.value).decode())
+    finally:
+        L.gdbamd_free(p)
+
+
 MERGE_STAT_NAMES = ("num_streams", "cells_in", "cells_out", "bytes_out", "tile", "ms_keys", "ms_rank", "ms_scan", "ms_gather", "s_h2d", "s_d2h", "s_total")
 
 

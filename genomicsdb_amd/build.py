@@ -14,7 +14,7 @@ OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(PKG, "libgenomicsdb_amd.so")
 TOOL = os.path.join(PKG, "gt_mpi_gather")
 TOOLS = {"gt_mpi_gather": TOOL, "vcf2tiledb": os.path.join(PKG, "vcf2tiledb"), "test_genomicsdb_importer": os.path.join(PKG, "test_genomicsdb_importer"),
-         "vcf_histogram": os.path.join(PKG, "vcf_histogram")}
+         "vcf_histogram": os.path.join(PKG, "vcf_histogram"), "vcfdiff": os.path.join(PKG, "vcfdiff")}
 
 SOURCES = [
     "kernels/gdb_pipeline.hip",
@@ -25,6 +25,7 @@ SOURCES = [
     "kernels/gdb_merge.hip",
     "kernels/gdb_split.hip",
     "kernels/gdb_histogram.hip",
+    "kernels/gdb_vcfdiff.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -183,6 +184,14 @@ def build_hostsim_histogram():
     d = os.path.join(ROOT, "tests", "hostsim_histogram")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "hostsim_histogram")
+
+
+def build_hostsim_vcfdiff():
+    """The bodies of the device vcfdiff (core/gdb_vcfdiff.hpp) as a stand-alone program built with the address and
+    undefined-behaviour sanitizers (tests only); -> program"""
+    d = os.path.join(ROOT, "tests", "hostsim_vcfdiff")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "hostsim_vcfdiff")
 
 
 def build_hostsim_inflate():

@@ -13,6 +13,7 @@
 #include "../kernels/gdb_bgzf.h"
 #include "../kernels/gdb_inflate.h"
 #include "../kernels/gdb_histogram.h"
+#include "../kernels/gdb_vcfdiff.h"
 #include "../kernels/gdb_split.h"
 #include "../host/vcf_importer.h"
 #include "../host/vcf_index.h"
@@ -623,6 +624,31 @@ int64_t gdbamd_histogram_text(const uint64_t* counts, uint64_t num_bins, int64_t
   const std::string out = histogram_text(counts, num_bins, (uint64_t)max_histogram_range);
   if (dst && cap) { const size_t n = std::min<size_t>(out.size(), (size_t)cap); memcpy(dst, out.data(), n); }
   return (int64_t)out.size();
+}
+int gdbamd_vcfdiff(const char* gold, const char* test, double threshold, const char* regions, int device, uint64_t text_budget_bytes, char** report_json,
+                   gdbamd_vcfdiff_stats* stats) {
+  try {
+    if (!gold || !test || !report_json) throw GenomicsDBConfigException("gdbamd_vcfdiff: null argument");
+    VcfDiffRequest req;
+    req.gold = gold; req.test = test; req.threshold = threshold;
+    if (regions) req.regions = regions;
+    req.device = device; req.text_budget_bytes = text_budget_bytes;
+    VcfDiffStats st;
+    const VcfDiffReport rep = vcfdiff_device(req, &st);
+    char* out = (char*)malloc(rep.json.size() + 1);
+    if (!out) throw GenomicsDBConfigException("gdbamd_vcfdiff: out of memory");
+    memcpy(out, rep.json.c_str(), rep.json.size() + 1);
+    *report_json = out;
+    if (stats) {
+      stats->gold_records = st.gold_records; stats->test_records = st.test_records;
+      stats->pairs_compared = st.pairs_compared; stats->pairs_light = st.pairs_light; stats->pairs_heavy = st.pairs_heavy;
+      stats->deferred = st.deferred; stats->events = st.events; stats->num_batches = st.num_batches; stats->resident_bytes = st.resident_bytes;
+      stats->ms_index = st.ms_index; stats->ms_inflate = st.ms_inflate; stats->ms_keys = st.ms_keys; stats->ms_compare = st.ms_compare;
+      stats->s_read = st.s_read; stats->s_walk = st.s_walk; stats->s_total = st.s_total;
+    }
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
 // ---- the streaming importer (api/genomicsdb_importer.h)
 void* gdbamd_importer_create(const char* loader_json, int rank, int device) {

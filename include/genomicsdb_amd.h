@@ -365,6 +365,27 @@ int gdbamd_input_histogram(const char* vid_mapping_file, const char* callset_map
 /* Histogram::print of the reference: "Histogram: [\n", then "lo,hi,count\n" for every non-zero bin (lo = b * size_of_bin, hi = (b + 1) * size_of_bin - 1), then
  * "]\n".  Returns the length of the text (dst may be NULL: call once to measure, once to write), -1 when num_bins is 0 or max_histogram_range negative */
 int64_t gdbamd_histogram_text(const uint64_t* counts, uint64_t num_bins, int64_t max_histogram_range, char* dst, uint64_t cap);
+/* vcfdiff on GPU `device` (kernels/gdb_vcfdiff.hip; reference tools/src/vcfdiff.cc): two VCF text files - plain, gzip or BGZF - compared record by record,
+ * the order of ALT alleles (AD / PL / AF and the like go through the allele permutation), of INFO keys, FORMAT keys and sample columns and float noise below
+ * `threshold` aside; DESIGN.md, "Comparing two VCFs", has the rule.  regions: NULL / "" or chr | chr:pos | chr:from-to | chr:from- , comma separated.
+ * *report_json is one JSON document, malloc'ed: release with gdbamd_free:
+ *   {"compared": pairs compared, "events": [{"kind": "COMPARED" | "REF_BLOCKS_OVERLAP" | "DIFFERENT_POSITIONS" | "EXTRA_LINES", "gold_line", "test_line" (1-based,
+ *    0: none), "gold_text", "test_text", and where a compare ran "flags": ["ID" | "ALLELES" | "QUAL" | "FILTER"], "info" and "format": {"MISSING_IN_TEST",
+ *    "ADDED_IN_TEST", "TYPE_DIFFERS", "DIFFERS": [field names]}}]}   in order; a COMPARED pair is listed only when a bit is set.
+ * Refused before anything runs: BCF2 input, differing or duplicate sample names, more than 64 distinct INFO or FORMAT names.  Errors that name file and
+ * 1-based line: a contig or an INFO / FORMAT key that the file's header lacks, fewer than 8 columns, POS / END that is no plain integer, a contig whose
+ * records are not contiguous or whose POS goes back.  Both files' text must fit in device memory.  stats may be NULL. */
+typedef struct gdbamd_vcfdiff_stats {
+  int64_t gold_records, test_records;           /* record lines inside the regions */
+  int64_t pairs_compared, pairs_light, pairs_heavy;  /* pairs; those on the lane-per-sample path; those on the wavefront-per-sample path */
+  int64_t deferred;                             /* float token pairs outside the device parser's exact range, decided by the host */
+  int64_t events, num_batches;
+  uint64_t resident_bytes;                      /* text and tab index kept on the device */
+  double ms_index, ms_inflate, ms_keys, ms_compare;  /* HIP-event ms per phase, summed */
+  double s_read, s_walk, s_total;               /* wall seconds of file read (+ host inflate), the host's walk, the whole call */
+} gdbamd_vcfdiff_stats;
+int gdbamd_vcfdiff(const char* gold, const char* test, double threshold, const char* regions, int device, uint64_t text_budget_bytes, char** report_json,
+                   gdbamd_vcfdiff_stats* stats);
 /* The streaming importer (GenomicsDBImporter, csrc/api/genomicsdb_importer.h; kernels/gdb_import_stream.hip): buffer streams of VCF text or BCF2
  * records imported batch by batch on one GPU with bounded device memory; INTEGRATION.md has the protocol.  loader_json: the path of a loader JSON, or
  * the JSON itself (a string that begins with '{').  device < 0: GDBAMD_DEVICE, else LOCAL_RANK, else 0.  Every call but create and destroy returns 0
