@@ -51,7 +51,8 @@ SYMBOLS = ["gdb_mi355_last_error", "gdb_mi355_device_count", "gdb_mi355_init", "
            "gdbamd_engine_column_histogram", "gdbamd_equi_partition_text", "gdbamd_build_output_index", "gdbamd_engine_print_calls", "gdbamd_engine_print_cells", "gdbamd_engine_query_variants", "gdbamd_pin_host_memory", "gdbamd_unpin_host_memory",
            "gdbamd_importer_create", "gdbamd_importer_add_buffer_stream", "gdbamd_importer_setup_loader", "gdbamd_importer_stream_file_idx", "gdbamd_importer_write",
            "gdbamd_importer_import_batch", "gdbamd_importer_is_done", "gdbamd_importer_finish", "gdbamd_importer_stats", "gdbamd_importer_destroy",
-           "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text", "gdbamd_vcfdiff"]
+           "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text", "gdbamd_vcfdiff",
+           "gdbamd_engine_columns_select", "gdbamd_engine_page_columns"]
 
 
 class HistogramStats(ctypes.Structure):
@@ -67,6 +68,25 @@ class VcfDiffStats(ctypes.Structure):
                 ("pairs_heavy", ctypes.c_int64), ("deferred", ctypes.c_int64), ("events", ctypes.c_int64), ("num_batches", ctypes.c_int64),
                 ("resident_bytes", ctypes.c_uint64), ("ms_index", ctypes.c_double), ("ms_inflate", ctypes.c_double), ("ms_keys", ctypes.c_double),
                 ("ms_compare", ctypes.c_double), ("s_read", ctypes.c_double), ("s_walk", ctypes.c_double), ("s_total", ctypes.c_double)]
+
+
+MAX_COLUMN_REQUESTS = 32      # GDBAMD_MAX_COLUMN_REQUESTS of include/genomicsdb_amd.h (tests/test_columns_bodies_cpu.py holds the two together)
+
+
+class ColumnRequest(ctypes.Structure):
+    """gdbamd_column_request of include/genomicsdb_amd.h"""
+    _fields_ = [("name", ctypes.c_char_p), ("dtype", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
+class Column(ctypes.Structure):
+    """gdbamd_column of include/genomicsdb_amd.h"""
+    _fields_ = [("name", ctypes.c_char_p), ("dtype", ctypes.c_int32), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int64 * 3), ("dev_ptr", ctypes.c_void_p)]
+
+
+class ColumnsStats(ctypes.Structure):
+    """gdbamd_columns_stats of include/genomicsdb_amd.h"""
+    _fields_ = [("records", ctypes.c_int64), ("bytes_read", ctypes.c_uint64), ("bytes_written", ctypes.c_uint64), ("ms_measure", ctypes.c_float),
+                ("ms_site", ctypes.c_float), ("ms_scatter", ctypes.c_float), ("n_fields", ctypes.c_int32), ("width", ctypes.c_int32 * MAX_COLUMN_REQUESTS)]
 
 
 def lib():
@@ -184,6 +204,8 @@ def lib():
     L.gdbamd_chromosome_intervals_for_column_partition.argtypes = [c.c_char_p, c.c_int, c.POINTER(c.c_void_p)]
     L.gdbamd_engine_prepare_interval.argtypes = [c.c_void_p, c.c_int64, c.c_int64]
     L.gdbamd_engine_next_page.argtypes = [c.c_void_p, c.c_uint64, c.POINTER(c.c_void_p), c.POINTER(c.c_uint64)]
+    L.gdbamd_engine_columns_select.argtypes = [c.c_void_p, c.POINTER(ColumnRequest), c.c_int]
+    L.gdbamd_engine_page_columns.argtypes = [c.c_void_p, c.POINTER(Column), c.c_int, c.POINTER(c.c_int), c.POINTER(ColumnsStats)]
     _lib = L
     return L
 

@@ -23,6 +23,18 @@ class _DevicePage:
         self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(addr), False), "version": 2}
 
 
+class _DeviceArray:
+    """a typed HBM array as an object torch can alias, like _DevicePage"""
+
+    def __init__(self, addr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": typestr, "data": (int(addr), False), "version": 2}
+
+
+# gdbamd dtype codes (include/genomicsdb_amd.h) <-> names, CUDA-array-interface type strings
+COLUMN_DTYPES = {"int8": 1, "int16": 2, "int32": 3, "int64": 4, "float32": 5, "uint8": 6}
+_COLUMN_TYPESTR = {1: "|i1", 2: "<i2", 3: "<i4", 4: "<i8", 5: "<f4", 6: "|u1"}
+
+
 class GenomicsDBQueryStream:
     """Byte stream of the combined gVCF (header first), the Python face of the six JNI entry points."""
 
@@ -332,6 +344,42 @@ class CombineEngine:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         for addr, n in self.pages(begin, end, arena_bytes):
             yield torch.as_tensor(_DevicePage(addr, n), device=dev)
+
+    def record_tensors(self, begin=0, end=INT64_MAX - 1, fields=None, arena_bytes=1 << 30, device=None, stats=None):
+        """The combined records of one column interval page by page as typed torch tensors that alias HBM (decoded on the device from the
+        BCF2 page; the engine's output format must be "bu").  Yields a dict name -> tensor: contig int32[R], pos / end / column int64[R],
+        qual float32[R], n_allele int32[R], alleles uint8[total] with alleles_off int64[R + 1], and per entry of `fields` - name ->
+        dtype name ("int8", "int16", "int32", "float32", None: the field's own), or name -> (dtype, width) - a FORMAT field as [R, N, W],
+        an INFO field as [R, W]; GT comes with GT_phase uint8[R, N, W].  Sentinels are BCF's for the dtype (missing -128 / -32768 /
+        -2**31 / 0x7F800001 as bits, end-of-vector the next value up; GT: -1 is missing).  A tensor is valid until the next iteration:
+        clone what has to live longer.  stats: a list that receives one dict of gdbamd_columns_stats per page."""
+        import torch
+        L = _lib.lib()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        names = list(fields or {})
+        req = (_lib.ColumnRequest * max(1, len(names)))()
+        for i, name in enumerate(names):
+            spec = (fields[name], 0) if not isinstance(fields[name], (tuple, list)) else fields[name]
+            if spec[0] is not None and spec[0] not in COLUMN_DTYPES:
+                raise GenomicsDBException("record_tensors: field %s: unknown dtype %r" % (name, spec[0]))
+            req[i].name, req[i].dtype, req[i].width = name.encode(), COLUMN_DTYPES.get(spec[0], 0), int(spec[1])
+        _check(L.gdbamd_engine_columns_select(self._e, req, len(names)) == 0, "record_tensors")
+        cols = (_lib.Column * (8 + 2 * len(names)))()
+        n, st = ctypes.c_int(), _lib.ColumnsStats()
+        for _ in self.pages(begin, end, arena_bytes):
+            _check(L.gdbamd_engine_page_columns(self._e, cols, len(cols), ctypes.byref(n), ctypes.byref(st)) == 0, "record_tensors")
+            out = {}
+            for c in cols[:n.value]:
+                shape = tuple(c.shape[:c.ndim])
+                tdtype = getattr(torch, [k for k, v in COLUMN_DTYPES.items() if v == c.dtype][0])
+                if 0 in shape:
+                    out[c.name.decode()] = torch.empty(shape, dtype=tdtype, device=dev)
+                else:
+                    out[c.name.decode()] = torch.as_tensor(_DeviceArray(c.dev_ptr, shape, _COLUMN_TYPESTR[c.dtype]), device=dev)
+            if stats is not None:
+                stats.append({"records": st.records, "bytes_read": st.bytes_read, "bytes_written": st.bytes_written, "ms_measure": st.ms_measure,
+                              "ms_site": st.ms_site, "ms_scatter": st.ms_scatter, "width": {name: st.width[i] for i, name in enumerate(names)}})
+            yield out
 
     def close(self):
         if self._e:

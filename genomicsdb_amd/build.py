@@ -26,6 +26,7 @@ SOURCES = [
     "kernels/gdb_split.hip",
     "kernels/gdb_histogram.hip",
     "kernels/gdb_vcfdiff.hip",
+    "kernels/gdb_columns.hip",
     "host/vid_mapper.cc",
     "host/variant_query_config.cc",
     "host/combine_plan.cc",
@@ -192,6 +193,14 @@ def build_hostsim_vcfdiff():
     d = os.path.join(ROOT, "tests", "hostsim_vcfdiff")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "hostsim_vcfdiff")
+
+
+def build_hostsim_columns():
+    """CPU harness around the bodies of the column decoder (core/gdb_columns.hpp) and the same source as a stand-alone program
+    built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_columns")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_columns.so"), os.path.join(d, "hostsim_columns_main")
 
 
 def build_hostsim_inflate():

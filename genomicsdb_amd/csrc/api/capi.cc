@@ -13,6 +13,9 @@
 #include "../kernels/gdb_bgzf.h"
 #include "../kernels/gdb_inflate.h"
 #include "../kernels/gdb_histogram.h"
+#include "../kernels/gdb_columns.h"
+
+static_assert(GDBAMD_MAX_COLUMN_REQUESTS == GDB_MAX_COLUMN_REQUESTS, "the public limit is the decoder's");
 #include "../kernels/gdb_vcfdiff.h"
 #include "../kernels/gdb_split.h"
 #include "../host/vcf_importer.h"
@@ -27,7 +30,12 @@ template <class F, class R> R guarded(F f, R on_error) {
   catch (const std::exception& e) { g_last_error = e.what(); return on_error; }
   catch (...) { g_last_error = "unknown exception"; return on_error; }
 }
-struct EngineHandle { std::unique_ptr<CombineEngine> eng; std::string calls_text; int calls_text_mode = -1; };   // calls_text: the document of gdbamd_engine_print_cells(mode) between its sizing and its copying call
+struct EngineHandle {
+  std::unique_ptr<CombineEngine> eng; std::string calls_text; int calls_text_mode = -1;
+  std::unique_ptr<RecordColumns> columns; bool has_page = false;      // the column decoder of gdbamd_engine_columns_select; has_page: next_page returned a page and no other call on the engine (staging, run_interval, the lanes, the printers) has come since
+};   // calls_text: the document of gdbamd_engine_print_cells(mode) between its sizing and its copying call
+// every entry point that stages, runs an interval or the lanes, prints or loads begins with this: the page next_page returned is no longer the caller's
+void page_gone(void* e) { if (e) ((EngineHandle*)e)->has_page = false; }
 }  // namespace
 
 extern "C" {
@@ -201,15 +209,20 @@ uint64_t gdbamd_engine_header(void* e, char* dst, uint64_t cap) {
   return h.size();
 }
 int gdbamd_engine_stage_cells(void* e, const uint8_t* cells, uint64_t nbytes) {
+  page_gone(e);
   return guarded([&]() -> int { ((EngineHandle*)e)->eng->stage_cells(cells, nbytes); return 0; }, 1);
 }
-int gdbamd_engine_stage_cells_begin(void* e) { return guarded([&]() -> int { ((EngineHandle*)e)->eng->stage_cells_begin(); return 0; }, 1); }
+int gdbamd_engine_stage_cells_begin(void* e) {
+  page_gone(e); return guarded([&]() -> int { ((EngineHandle*)e)->eng->stage_cells_begin(); return 0; }, 1); }
 int gdbamd_engine_stage_cells_append(void* e, const uint8_t* cells, uint64_t nbytes) {
+  page_gone(e);
   return guarded([&]() -> int { ((EngineHandle*)e)->eng->stage_cells_append(cells, nbytes); return 0; }, 1);
 }
-int gdbamd_engine_stage_cells_end(void* e) { return guarded([&]() -> int { ((EngineHandle*)e)->eng->stage_cells_end(); return 0; }, 1); }
+int gdbamd_engine_stage_cells_end(void* e) {
+  page_gone(e); return guarded([&]() -> int { ((EngineHandle*)e)->eng->stage_cells_end(); return 0; }, 1); }
 int gdbamd_engine_adopt_device_fragment(void* e, int64_t ncells, const int32_t* row, const int64_t* begin, const int64_t* end, const gdbamd_device_column* cols,
                                         int ncols, uint64_t reference_cell_bytes) {
+  page_gone(e);
   return guarded([&]() -> int {
     CombineEngine& eng = *((EngineHandle*)e)->eng;
     if (ncols != eng.plan().plan.nfields) throw GenomicsDBDeviceException("adopt_device_fragment: ncols != number of plan fields");
@@ -224,8 +237,10 @@ int gdbamd_engine_adopt_device_fragment(void* e, int64_t ncells, const int32_t* 
     return 0;
   }, 1);
 }
-int gdbamd_engine_open_array(void* e, const char* dir) { return guarded([&]() -> int { ((EngineHandle*)e)->eng->open_array(dir ? dir : ""); return 0; }, 1); }
+int gdbamd_engine_open_array(void* e, const char* dir) {
+  page_gone(e); return guarded([&]() -> int { ((EngineHandle*)e)->eng->open_array(dir ? dir : ""); return 0; }, 1); }
 int gdbamd_engine_open_memory_cells(void* e, const uint8_t* cells, uint64_t nbytes) {
+  page_gone(e);
   return guarded([&]() -> int { ((EngineHandle*)e)->eng->open_memory_cells(cells, nbytes); return 0; }, 1);
 }
 int gdbamd_pin_host_memory(const void* p, uint64_t nbytes) {
@@ -242,9 +257,11 @@ int gdbamd_unpin_host_memory(const void* p) {
   }, 1);
 }
 int gdbamd_engine_open_cell_callback(void* e, gdbamd_cell_chunk_fn fn, void* user) {
+  page_gone(e);
   return guarded([&]() -> int { ((EngineHandle*)e)->eng->open_cell_callback(fn, user); return 0; }, 1);
 }
 int gdbamd_engine_cover(void* e, int64_t column, int64_t* lo, int64_t* hi) {
+  page_gone(e);
   return guarded([&]() -> int {
     const CombineEngine::Coverage c = ((EngineHandle*)e)->eng->cover(column);
     if (lo) *lo = c.lo;
@@ -260,6 +277,7 @@ int gdbamd_engine_staged_info(void* e, int64_t* ncells, uint64_t* reference_cell
   return 0;
 }
 int gdbamd_engine_set_reference(void* e, int64_t begin, const char* bases, uint64_t len) {
+  page_gone(e);
   return guarded([&]() -> int { ((EngineHandle*)e)->eng->set_reference_window(begin, std::string(bases, len)); return 0; }, 1);
 }
 
@@ -290,6 +308,7 @@ static void fill_interval_stats(gdbamd_interval_stats* out, const IntervalStats&
 }
 int gdbamd_engine_run_interval(void* e, int64_t qb, int64_t qe, uint64_t arena_bytes, char* host_out, uint64_t host_cap, uint64_t* host_len,
                                gdbamd_interval_stats* out) {
+  page_gone(e);
   return guarded([&]() -> int {
     CombineEngine& eng = *((EngineHandle*)e)->eng;
     HostCopy hc{host_out, host_cap, 0};
@@ -302,6 +321,7 @@ int gdbamd_engine_run_interval(void* e, int64_t qb, int64_t qe, uint64_t arena_b
 }
 int gdbamd_engine_run_intervals(void* e, int n, const int64_t* begins, const int64_t* ends, uint64_t arena_bytes, int lanes, gdbamd_interval_stats* stats,
                                 char* const* host_out, const uint64_t* host_cap, uint64_t* host_len) {
+  page_gone(e);
   return guarded([&]() -> int {
     CombineEngine& eng = *((EngineHandle*)e)->eng;
     std::vector<std::pair<int64_t, int64_t>> ivs;
@@ -323,12 +343,14 @@ int gdbamd_engine_lane_footprint(void* e, int64_t interval_columns, uint64_t are
   return guarded([&]() -> int { *bytes = ((EngineHandle*)e)->eng->lane_footprint_bytes(interval_columns, arena_bytes); return 0; }, -1);
 }
 int gdbamd_engine_release_lanes(void* e) {
+  page_gone(e);
   return guarded([&]() -> int { ((EngineHandle*)e)->eng->release_lanes(); return 0; }, -1);
 }
 
 int gdbamd_engine_prepare_interval(void* e, int64_t qb, int64_t qe) {
   return guarded([&]() -> int {
     CombineEngine& eng = *((EngineHandle*)e)->eng;
+    ((EngineHandle*)e)->has_page = false;
     eng.stage_reference_for(qb, qe);
     eng.pipeline().prepare_interval(qb, qe);
     return 0;
@@ -338,10 +360,47 @@ int gdbamd_engine_next_page(void* e, uint64_t arena_bytes, const void** dev_ptr,
   return guarded([&]() -> int {
     const char* p = nullptr;
     uint64_t n = 0;
+    ((EngineHandle*)e)->has_page = false;
     const bool more = ((EngineHandle*)e)->eng->pipeline().next_page(arena_bytes, &p, &n);
+    ((EngineHandle*)e)->has_page = more;
     if (dev_ptr) *dev_ptr = more ? p : nullptr;
     if (nbytes) *nbytes = more ? n : 0;
     return more ? 1 : 0;
+  }, -1);
+}
+
+int gdbamd_engine_columns_select(void* e, const gdbamd_column_request* requests, int n) {
+  return guarded([&]() -> int {
+    EngineHandle* h = (EngineHandle*)e;
+    if (n < 0 || (n > 0 && !requests)) throw GenomicsDBDeviceException("columns_select: no requests given");
+    std::vector<ColumnRequest> rq;
+    for (int i = 0; i < n; ++i) { ColumnRequest r; r.name = requests[i].name ? requests[i].name : ""; r.dtype = requests[i].dtype; r.width = requests[i].width; rq.push_back(r); }
+    h->columns.reset();
+    h->columns.reset(new RecordColumns(h->eng->plan(), h->eng->device(), rq));
+    return 0;
+  }, -1);
+}
+int gdbamd_engine_page_columns(void* e, gdbamd_column* out_columns, int cap, int* n, gdbamd_columns_stats* stats) {
+  return guarded([&]() -> int {
+    EngineHandle* h = (EngineHandle*)e;
+    if (!h->columns) throw GenomicsDBDeviceException("page_columns: no fields chosen: call gdbamd_engine_columns_select first");
+    if (!h->has_page) throw GenomicsDBDeviceException("page_columns: there is no page: gdbamd_engine_next_page has not returned one, or the interval is exhausted");
+    ColumnsStats cs;
+    const std::vector<RecordColumn>& cols = h->columns->decode(h->eng->pipeline().last_page(), &cs);
+    if (n) *n = (int)cols.size();
+    for (int i = 0; out_columns && i < cap && i < (int)cols.size(); ++i) {
+      const RecordColumn& c = cols[(size_t)i];
+      out_columns[i].name = c.name.c_str(); out_columns[i].dtype = c.dtype; out_columns[i].ndim = c.ndim;
+      for (int k = 0; k < 3; ++k) out_columns[i].shape[k] = c.shape[k];
+      out_columns[i].dev_ptr = c.dev_ptr;
+    }
+    if (stats) {
+      memset(stats, 0, sizeof(*stats));
+      stats->records = cs.records; stats->bytes_read = cs.bytes_read; stats->bytes_written = cs.bytes_written;
+      stats->ms_measure = cs.ms_measure; stats->ms_site = cs.ms_site; stats->ms_scatter = cs.ms_scatter; stats->n_fields = cs.n_fields;
+      for (int i = 0; i < GDBAMD_MAX_COLUMN_REQUESTS; ++i) stats->width[i] = cs.width[i];
+    }
+    return 0;
   }, -1);
 }
 
@@ -349,6 +408,7 @@ int gdbamd_engine_split_point(void* engine, int64_t qb, int64_t qe, int64_t max_
   try { *piece_end = ((EngineHandle*)engine)->eng->pipeline().split_point(qb, qe, max_columns); return 0; } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
 int gdbamd_engine_column_histogram(void* engine, uint64_t hist_begin, uint64_t hist_end, uint64_t bin_size, uint64_t* counts, uint64_t nbins, int accumulate) {
+  page_gone(engine);
   try { ((EngineHandle*)engine)->eng->pipeline().column_histogram(hist_begin, hist_end, bin_size, counts, nbins, accumulate != 0); return 0; } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
 // gt_mpi_gather --print-calls: the document is produced by the call with dst == NULL (which returns its length) and kept in the handle
@@ -356,6 +416,7 @@ int gdbamd_engine_column_histogram(void* engine, uint64_t hist_begin, uint64_t h
 int64_t gdbamd_engine_print_calls(void* engine, char* dst, uint64_t cap) { return gdbamd_engine_print_cells(engine, 0, dst, cap); }
 // mode 0: --print-calls, 1: --print-csv, 2: --print-AC
 int64_t gdbamd_engine_print_cells(void* engine, int mode, char* dst, uint64_t cap) {
+  page_gone(engine);
   try {
     EngineHandle* h = (EngineHandle*)engine;
     auto make = [&]() { h->calls_text_mode = mode; return mode == 0 ? h->eng->print_calls() : mode == 1 ? h->eng->print_csv() : h->eng->print_allele_counts(); };
@@ -371,6 +432,7 @@ int64_t gdbamd_engine_print_cells(void* engine, int mode, char* dst, uint64_t ca
 }
 // gt_mpi_gather without a mode flag: the variants document, same two-call convention (kept in the handle as "mode 3")
 int64_t gdbamd_engine_query_variants(void* engine, char* dst, uint64_t cap) {
+  page_gone(engine);
   try {
     EngineHandle* h = (EngineHandle*)engine;
     auto make = [&]() { h->calls_text_mode = 3; return h->eng->query_variants(); };
@@ -419,6 +481,7 @@ int gdbamd_engine_save_fragment_compressed(void* engine, const char* path) {
   try { ((EngineHandle*)engine)->eng->save_fragment(path, true); return 0; } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
 int gdbamd_engine_load_fragment(void* engine, const char* path) {
+  page_gone(engine);
   try { ((EngineHandle*)engine)->eng->load_fragment(path); return 0; } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
 

@@ -33,6 +33,7 @@ class CombineEngine {
   VariantQueryConfig& query_config() { return m_qc; }
   const HostPlan& plan() const { return m_hp; }
   DevicePipeline& pipeline() { return *m_pipe; }
+  int device() const { return m_device; }
   void stage_cells(const uint8_t* cells, uint64_t nbytes);
   // staging in parts: cells of successive calls must continue the column-major order
   void stage_cells_begin();

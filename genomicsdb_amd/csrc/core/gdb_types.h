@@ -33,6 +33,7 @@
 #define GDB_MAX_PIPELINES_PER_PROCESS 256  // elements of the __constant__ context array (kernels/gdb_pipeline.hip: c_ex), one per live pipeline (on gfx9 the constant
                                            // address space is ordinary device memory read with scalar loads: nothing limits it to 64 KB)
 #define GDB_MAX_HISTOGRAM_FIELDS 8  // composite (bins, counts) INFO fields reduced with histogram_sum
+#define GDB_MAX_COLUMN_REQUESTS 32  // fields of one selection of the column decoder (core/gdb_columns.hpp)
 
 // htslib / TileDB sentinels (reference include/vcf/vcf.h:59-218)
 #define GDB_BCF_INT32_MISSING ((int32_t)0x80000000)

@@ -153,6 +153,11 @@ class DevicePipeline {
   // hip_event (hipEvent_t) marks the consumer's last read of the arena; the next begin_page() into it waits for the event on the compute stream
   void set_arena_release_event(int arena_idx, void* hip_event);
   const IntervalStats& interval_stats() const;
+  // read-only view of the page most recently produced (valid until the next page is begun): records [first, last) of the interval, the
+  // page in HBM, and the interval's record offsets (device pointer, P + 1 of them; record k begins at page + rec_off[k] - base) - what
+  // the column decoder (kernels/gdb_columns.h) reads.  valid = false: no page yet
+  struct PageView { bool valid = false; int64_t first = 0, last = 0; uint64_t base = 0; const uint64_t* rec_off = nullptr; const char* page = nullptr; uint64_t nbytes = 0; };
+  PageView last_page() const;
   // the staged fragment as device pointers (owned by this pipeline: valid until it stages, loads or adopts another one) and a counter
   // of the fragments held so far - what a second pipeline needs to work on the same fragment (adopt_fragment; CombineEngine::run_intervals)
   FragmentView fragment_view() const;

@@ -3838,6 +3838,7 @@ struct DevicePipeline::Impl {
     AssemblySizing sz{};
     int NT = 0, bcf_F = 0; BcfLayout lay{nullptr, nullptr, nullptr, nullptr};
     EventBuf eb{nullptr, nullptr, nullptr, 0};
+    DevicePipeline::PageView last_page;      // what begin_page produced last (last_page())
   } iv;
   // the resolved (record, sample) matrix in the layout the interval's sizing chose
   ResMatrix res_view() const { return iv.sz.res_compact ? ResMatrix{nullptr, res_off.p, res_len8.p} : ResMatrix{resolved.p, nullptr, nullptr}; }
@@ -6073,6 +6074,7 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
   if (st_w != st) { HIP_CHECK(hipEventRecord(S.ev_page_join, st_w)); HIP_CHECK(hipStreamWaitEvent(st, S.ev_page_join, 0)); }
   HIP_CHECK(hipMemcpyAsync(&S.hb->page_err[ai], S.err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipEventRecord(w[3], st));
+  iv.last_page = PageView{true, kp, ke, page_base, (const uint64_t*)S.rec_off.p, arena, page_bytes};
   iv.kp = ke;
   ticket->arena = ai; ticket->dev = arena; ticket->nbytes = page_bytes; ticket->done_event = (void*)w[3]; S.queue_compression(ai, arena, page_bytes);
   return true;
@@ -6115,6 +6117,7 @@ bool DevicePipeline::next_page(uint64_t arena_bytes, const char** dev_ptr, uint6
 }
 
 const IntervalStats& DevicePipeline::interval_stats() const { return m_->iv.stats; }
+DevicePipeline::PageView DevicePipeline::last_page() const { return m_->iv.last_page; }
 FragmentView DevicePipeline::fragment_view() const { return m_->fr; }
 uint64_t DevicePipeline::fragment_generation() const { return m_->fragment_generation; }
 void DevicePipeline::set_page_priority(bool on) { m_->page_priority = on; }

@@ -249,6 +249,47 @@ int gdbamd_engine_release_lanes(void* engine);
 int gdbamd_engine_prepare_interval(void* engine, int64_t column_begin, int64_t column_end);
 int gdbamd_engine_next_page(void* engine, uint64_t arena_bytes, const void** dev_ptr, uint64_t* nbytes);
 
+/* ---- the page as typed columns in HBM ---------------------------------------------------------------------
+ * For consumers on the GPU (a genotype matrix, a filter, a model): the page gdbamd_engine_next_page has just returned, decoded on the device
+ * into typed arrays that never pass through text or the host.  The engine's output format must be "bu": the decoder reads the BCF2 records
+ * where they lie (BCFv2.2 layout: typed descriptors, int8 / int16 / int32 / float / char vectors, one block per FORMAT field).
+ * With R = records of the page and N = samples of the query, every page gives
+ *   contig int32[R] (the BCF rid), pos int64[R] (1-based), end int64[R] (pos + rlen - 1), column int64[R] (TileDB column of pos),
+ *   qual float32[R] (bit pattern kept; missing = 0x7F800001), n_allele int32[R], alleles uint8[total] with alleles_off int64[R + 1]
+ *   (REF and the ALTs of record r joined by ',' are alleles[alleles_off[r] .. alleles_off[r + 1]))
+ * and per requested field, in request order: a FORMAT field as [R, N, W], an INFO field as [R, W]; "GT" as the allele indices (-1: missing)
+ * followed by GT_phase uint8[R, N, W] (the phase bit of every element; 0 where it is missing or behind the end).
+ * Sentinels are BCF's own for the column's dtype: missing -128 / -32768 / INT32_MIN / 0x7F800001, end-of-vector the next value up.  Elements
+ * behind a vector's end up to W are end-of-vector; a field that a record does not have is [missing, end-of-vector, ...] for every sample.
+ * Nothing is truncated or wrapped: a vector longer than a given width, and an integer outside the dtype (htslib's bounds: int8 holds
+ * -120 .. 127, int16 -32760 .. 32767), are errors that name the field and the pos of the smallest offending record. */
+enum { GDBAMD_DTYPE_DEFAULT = 0, GDBAMD_DTYPE_INT8 = 1, GDBAMD_DTYPE_INT16 = 2, GDBAMD_DTYPE_INT32 = 3, GDBAMD_DTYPE_INT64 = 4, GDBAMD_DTYPE_FLOAT32 = 5, GDBAMD_DTYPE_UINT8 = 6 };
+#define GDBAMD_MAX_COLUMN_REQUESTS 32
+/* name: "GT" or the id of an Integer or Float FORMAT or INFO line of the engine's header; an id that is both (DP) means the FORMAT field,
+ * "INFO/DP" and "FORMAT/DP" say which.  dtype: INT8 / INT16 / INT32 for integers (DEFAULT: INT32), FLOAT32 or DEFAULT for floats.
+ * width: W; 0 = the longest vector of the field in the page (at least 1) */
+typedef struct gdbamd_column_request { const char* name; int32_t dtype; int32_t width; } gdbamd_column_request;
+/* name: owned by the engine, valid as long as dev_ptr */
+typedef struct gdbamd_column { const char* name; int32_t dtype; int32_t ndim; int64_t shape[3]; void* dev_ptr; } gdbamd_column;
+typedef struct gdbamd_columns_stats {
+  int64_t records;
+  uint64_t bytes_read;                   /* what the decoder read of the page: the shared blocks and the blocks of the requested FORMAT fields */
+  uint64_t bytes_written;                /* all columns */
+  float ms_measure, ms_site, ms_scatter; /* hipEvent time of the per-record walk + the scan of the allele lengths, the site columns, the field columns */
+  int32_t n_fields;
+  int32_t width[GDBAMD_MAX_COLUMN_REQUESTS];   /* W of every requested field, in request order */
+} gdbamd_columns_stats;
+/* Chooses the fields (n may be 0: the site columns alone).  Refused by name, before anything is launched: a string or Flag field, ID and
+ * FILTER, a name that is neither a FORMAT nor an INFO id of the header, a dtype the field cannot have, an engine whose output format is not
+ * "bu" or that was created with use_missing_values_only_not_vector_end.  0, or -1 with gdb_mi355_last_error(). */
+int gdbamd_engine_columns_select(void* engine, const gdbamd_column_request* requests, int n);
+/* Decodes the page last returned by gdbamd_engine_next_page.  out_columns[0 .. min(cap, *n)) are filled, *n is their number (8 + one per
+ * field + one for GT_phase).  The columns lie in buffers the engine owns and grows on demand (checked against the free device memory first;
+ * refused with the sizes when they do not fit); they are valid until the next page is asked for (a buffer that has to grow is freed first: the pointers of the page before are gone then, also within
+ * one interval).  Any other call on the engine after gdbamd_engine_next_page - staging, run_interval, the lanes, the printers - takes the page away.  Without a page, or before
+ * gdbamd_engine_columns_select: an error.  0, or -1. */
+int gdbamd_engine_page_columns(void* engine, gdbamd_column* out_columns, int cap, int* n, gdbamd_columns_stats* stats);
+
 /* ---- (3) host-only helpers (no device needed) ----------------------------------------------------------- */
 /* column partition of `rank` as the loader JSON defines it: begin from "column_partitions"[rank], end = next sorted begin - 1
  * (reference: GenomicsDBImportConfig::get_column_partition, src/main/cpp/src/config/json_config.cc:340-417) */
