@@ -52,6 +52,7 @@ SYMBOLS = ["gdb_mi355_last_error", "gdb_mi355_device_count", "gdb_mi355_init", "
            "gdbamd_importer_create", "gdbamd_importer_add_buffer_stream", "gdbamd_importer_setup_loader", "gdbamd_importer_stream_file_idx", "gdbamd_importer_write",
            "gdbamd_importer_import_batch", "gdbamd_importer_is_done", "gdbamd_importer_finish", "gdbamd_importer_stats", "gdbamd_importer_destroy",
            "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text", "gdbamd_vcfdiff",
+           "gdbamd_index_vcf_device", "gdbamd_split_files_device_index",
            "gdbamd_engine_columns_select", "gdbamd_engine_page_columns"]
 
 
@@ -60,6 +61,14 @@ class HistogramStats(ctypes.Structure):
     _fields_ = [("num_files", ctypes.c_int64), ("num_records", ctypes.c_int64), ("num_counted", ctypes.c_int64), ("total_weight", ctypes.c_uint64),
                 ("num_batches", ctypes.c_int64), ("num_atomics", ctypes.c_int64), ("ms_index", ctypes.c_double), ("ms_inflate", ctypes.c_double),
                 ("ms_histogram", ctypes.c_double), ("s_read", ctypes.c_double), ("s_h2d", ctypes.c_double), ("s_total", ctypes.c_double)]
+
+
+class IndexStats(ctypes.Structure):
+    """gdbamd_index_stats of include/genomicsdb_amd.h"""
+    _fields_ = [("members", ctypes.c_int64), ("batches", ctypes.c_int64), ("lines", ctypes.c_int64), ("records", ctypes.c_int64), ("contigs", ctypes.c_int64),
+                ("bins", ctypes.c_int64), ("chunks", ctypes.c_int64), ("linear_windows", ctypes.c_int64), ("text_bytes", ctypes.c_uint64), ("atomics", ctypes.c_int64),
+                ("ms_inflate", ctypes.c_double), ("ms_index", ctypes.c_double), ("ms_records", ctypes.c_double), ("ms_chunks", ctypes.c_double),
+                ("ms_linear", ctypes.c_double), ("s_read", ctypes.c_double), ("s_serialize_write", ctypes.c_double), ("s_total", ctypes.c_double)]
 
 
 class VcfDiffStats(ctypes.Structure):
@@ -183,6 +192,9 @@ def lib():
                                      c.POINTER(c.c_double), c.c_int]
     L.gdbamd_split_files_device.argtypes = [c.c_char_p, c.c_char_p, c.c_char_p, c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64), c.c_int, c.c_char_p, c.c_char_p, c.c_int,
                                             c.c_uint64, c.c_int, c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_double), c.c_int, c.POINTER(c.c_void_p)]
+    L.gdbamd_split_files_device_index.argtypes = L.gdbamd_split_files_device.argtypes + [c.c_int]
+    L.gdbamd_index_vcf_device.argtypes = [c.c_char_p, c.c_int, c.c_uint64, c.POINTER(IndexStats)]
+    L.gdbamd_build_output_index.argtypes = [c.c_char_p, c.c_int]
     L.gdbamd_input_histogram.argtypes = [c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_uint64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int, c.c_uint64, c.c_int,
                                          c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_void_p), c.POINTER(c.c_uint64), c.c_void_p, c.POINTER(HistogramStats)]
     L.gdbamd_vcfdiff.argtypes = [c.c_char_p, c.c_char_p, c.c_double, c.c_char_p, c.c_int, c.c_uint64, c.POINTER(c.c_void_p), c.POINTER(VcfDiffStats)]

@@ -577,11 +577,11 @@ def chromosome_intervals(loader_json, rank=0):
 
 
 SPLIT_STAT_NAMES = ("num_files", "num_record_lines", "num_lines_written", "text_bytes_in", "text_bytes_out", "compressed_bytes_out", "num_batches", "ms_index",
-                    "ms_classify", "ms_scan_gather", "ms_deflate", "s_read", "s_h2d", "s_d2h_write", "s_index_build", "s_total", "ms_inflate")
+                    "ms_classify", "ms_scan_gather", "ms_deflate", "s_read", "s_h2d", "s_d2h_write", "s_index_build", "s_total", "ms_inflate", "ms_index_kernels")
 
 
 def split_files(vid_mapping_file, callset_mapping_file, partitions, results_directory=None, file_root="", produce=None, device=0, text_budget_bytes=0, stats=None,
-                output_filename=None, extra_files=(), inflate="auto"):
+                output_filename=None, extra_files=(), inflate="auto", index_on_device=False):
     """vcf2tiledb --split-files on GPU `device` (kernels/gdb_split.hip): every (g)VCF text file of the callset mapping (plain, gzip or
     BGZF), then `extra_files`, cut into one BGZF file + .tbi per column partition in one pass per file.  partitions: [(begin, end)]
     per partition index, as the loader JSON's column_partitions give them with derived ends (column_partition()).  A partition's
@@ -590,7 +590,10 @@ def split_files(vid_mapping_file, callset_mapping_file, partitions, results_dire
     Outputs: <results_directory or the input's directory>/partition_<p>_<basename>, or what the callset mapping's
     "split_files_paths" names; output_filename names the output of exactly one input and one partition.
     -> {(original filename, partition index): output path}.  BCF2 and CSV inputs are refused by name; a line error names file
-    and line and leaves no output of that input.  `stats`, a dict, receives SPLIT_STAT_NAMES."""
+    and line and leaves no output of that input.  index_on_device: each output's .tbi is built on the GPU while the output is written
+    (kernels/gdb_index.hip), from its text that is still in device memory and the blocks just deflated, instead of by the host builder
+    re-reading the finished file; the files are the same, byte for byte.  `stats`, a dict, receives SPLIT_STAT_NAMES (s_index_build:
+    wall clock of index building on either path, ms_index_kernels: its device share)."""
     if inflate not in INFLATE_MODES:
         raise ValueError("inflate=%r: one of %s" % (inflate, sorted(INFLATE_MODES)))
     L = _lib.lib()
@@ -602,9 +605,10 @@ def split_files(vid_mapping_file, callset_mapping_file, partitions, results_dire
     extra_arr = (ctypes.c_char_p * max(len(extra), 1))(*extra)
     st = (ctypes.c_double * len(SPLIT_STAT_NAMES))()
     out = ctypes.c_void_p()
-    rc = L.gdbamd_split_files_device(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), n, begins, ends,
+    rc = L.gdbamd_split_files_device_index(os.fsencode(vid_mapping_file), os.fsencode(callset_mapping_file), os.fsencode(file_root or ""), n, begins, ends,
                                      -1 if produce is None else int(produce), os.fsencode(results_directory or ""), os.fsencode(output_filename or ""), int(device),
-                                     int(text_budget_bytes), INFLATE_MODES[inflate], len(extra), extra_arr, st, len(SPLIT_STAT_NAMES), ctypes.byref(out))
+                                     int(text_budget_bytes), INFLATE_MODES[inflate], len(extra), extra_arr, st, len(SPLIT_STAT_NAMES), ctypes.byref(out),
+                                           1 if index_on_device else 0)
     _check(rc == 0, "split_files")
     try:
         text = ctypes.string_at(out.value).decode()
@@ -617,6 +621,24 @@ def split_files(vid_mapping_file, callset_mapping_file, partitions, results_dire
         original, p, path = line.split("\t")
         result[(original, int(p))] = path
     return result
+
+
+INDEX_STAT_NAMES = tuple(name for name, _ in _lib.IndexStats._fields_)
+
+
+def index_vcf(path, device=0, text_budget_bytes=0, stats=None):
+    """<path>.tbi of a bgzipped VCF, built on GPU `device` (kernels/gdb_index.hip): the file the host builder writes, byte for byte.  The
+    file crosses the link compressed and is inflated and indexed on the device in batches of whole lines of about text_budget_bytes
+    (0: 64 MiB); the result does not depend on where the batches are cut.  Refused: a file that is not BGZF from its first byte to its
+    last (the error names the byte offset), a member with a bad stream, ISIZE or CRC32, a record with POS < 1 or POS / END >= 2^31 (file
+    and 1-based line); after an error no .tbi exists.  -> the index path.  `stats`, a dict, receives INDEX_STAT_NAMES."""
+    L = _lib.lib()
+    st = _lib.IndexStats()
+    rc = L.gdbamd_index_vcf_device(os.fsencode(path), int(device), int(text_budget_bytes), ctypes.byref(st))
+    _check(rc == 0, "index_vcf")
+    if stats is not None:
+        stats.update({k: getattr(st, k) for k in INDEX_STAT_NAMES})
+    return os.fspath(path) + ".tbi"
 
 
 HISTOGRAM_STAT_NAMES = tuple(name for name, _ in _lib.HistogramStats._fields_)

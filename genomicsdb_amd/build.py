@@ -25,6 +25,7 @@ SOURCES = [
     "kernels/gdb_merge.hip",
     "kernels/gdb_split.hip",
     "kernels/gdb_histogram.hip",
+    "kernels/gdb_index.hip",
     "kernels/gdb_vcfdiff.hip",
     "kernels/gdb_columns.hip",
     "host/vid_mapper.cc",
@@ -34,6 +35,7 @@ SOURCES = [
     "host/reference_genome.cc",
     "host/vcf_importer.cc",
     "host/vcf_index.cc",
+    "host/bgzf_host.cc",
     "api/genomicsdb_bcf_generator.cc",
     "api/genomicsdb_operators.cc",
     "api/genomicsdb_importer.cc",
@@ -185,6 +187,14 @@ def build_hostsim_histogram():
     d = os.path.join(ROOT, "tests", "hostsim_histogram")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "hostsim_histogram")
+
+
+def build_hostsim_index():
+    """CPU harness around the bodies of the device tabix builder (core/gdb_index.hpp) with the shared serialiser, and the same source
+    as a stand-alone program built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_index")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_index.so"), os.path.join(d, "hostsim_index")
 
 
 def build_hostsim_vcfdiff():

@@ -13,6 +13,7 @@
 #include "../kernels/gdb_bgzf.h"
 #include "../kernels/gdb_inflate.h"
 #include "../kernels/gdb_histogram.h"
+#include "../kernels/gdb_index.h"
 #include "../kernels/gdb_columns.h"
 
 static_assert(GDBAMD_MAX_COLUMN_REQUESTS == GDB_MAX_COLUMN_REQUESTS, "the public limit is the decoder's");
@@ -614,6 +615,13 @@ int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nb
 int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
                               const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
                               uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs) {
+  return gdbamd_split_files_device_index(vid_mapping_file, callset_mapping_file, file_root, npartitions, begins, ends, produce, results_directory, single_output_name, device,
+                                         text_budget_bytes, inflate_mode, nextra, extra_paths, stats, std::min<int>(nstats, GDBAMD_SPLIT_NUM_STATS), outputs, 0);
+}
+int gdbamd_split_files_device_index(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
+                                    const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
+                                    uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs,
+                                    int index_on_device) {
   try {
     if (!vid_mapping_file || !callset_mapping_file || npartitions <= 0 || !begins || !ends) throw GenomicsDBConfigException("gdbamd_split_files_device: null argument or no partition");
     if (nextra < 0 || (nextra > 0 && !extra_paths)) throw GenomicsDBConfigException("gdbamd_split_files_device: null extra_paths");
@@ -628,6 +636,7 @@ int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_
     if (single_output_name) req.single_output = single_output_name;
     for (int i = 0; i < nextra; ++i) { if (!extra_paths[i]) throw GenomicsDBConfigException("gdbamd_split_files_device: null extra path"); req.extra_paths.push_back(extra_paths[i]); }
     req.device = device; req.text_budget_bytes = text_budget_bytes; req.inflate_mode = inflate_mode;
+    req.index_on_device = index_on_device != 0;
     SplitStats st;
     const std::vector<SplitOutput> done = split_files_device(vid, req, &st);
     if (outputs) {
@@ -638,10 +647,26 @@ int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_
       memcpy(*outputs, text.c_str(), text.size() + 1);
     }
     if (stats && nstats > 0) {
-      const double v[GDBAMD_SPLIT_NUM_STATS] = {(double)st.num_files, (double)st.num_record_lines, (double)st.num_lines_written, (double)st.text_bytes_in, (double)st.text_bytes_out,
+      const double v[GDBAMD_SPLIT_INDEX_NUM_STATS] = {(double)st.num_files, (double)st.num_record_lines, (double)st.num_lines_written, (double)st.text_bytes_in, (double)st.text_bytes_out,
                                                 (double)st.compressed_bytes_out, (double)st.num_batches, st.ms_index, st.ms_classify, st.ms_scan_gather, st.ms_deflate,
-                                                st.s_read, st.s_h2d, st.s_d2h_write, st.s_index_build, st.s_total, st.ms_inflate};
-      memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_SPLIT_NUM_STATS));
+                                                st.s_read, st.s_h2d, st.s_d2h_write, st.s_index_build, st.s_total, st.ms_inflate, st.ms_index_kernels};
+      memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_SPLIT_INDEX_NUM_STATS));
+    }
+    g_last_error.clear();
+    return 0;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int gdbamd_index_vcf_device(const char* path, int device, uint64_t text_budget_bytes, gdbamd_index_stats* stats) {
+  try {
+    if (!path) throw GenomicsDBConfigException("gdbamd_index_vcf_device: null path");
+    IndexStats st;
+    index_vcf_device(path, device, text_budget_bytes, &st);
+    if (stats) {
+      stats->members = st.members; stats->batches = st.batches; stats->lines = st.lines; stats->records = st.records;
+      stats->contigs = st.contigs; stats->bins = st.bins; stats->chunks = st.chunks; stats->linear_windows = st.linear_windows;
+      stats->text_bytes = st.text_bytes; stats->atomics = st.atomics;
+      stats->ms_inflate = st.ms_inflate; stats->ms_index = st.ms_index; stats->ms_records = st.ms_records; stats->ms_chunks = st.ms_chunks; stats->ms_linear = st.ms_linear;
+      stats->s_read = st.s_read; stats->s_serialize_write = st.s_serialize_write; stats->s_total = st.s_total;
     }
     g_last_error.clear();
     return 0;

@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "../core/gdb_index_types.h"
 #include "../kernels/gdb_bgzf.h"
 
 namespace genomicsdb_amd {
@@ -26,14 +27,8 @@ int reg2bin(int64_t beg, int64_t end) {
 }
 int bin_first(int l) { return ((1 << (3 * l)) - 1) / 7; }
 // level of a bin and the first position it covers -> used for CSI's per-bin loffset
-struct Chunk { uint64_t beg, end; };
-struct RefIndex {
-  std::map<uint32_t, std::vector<Chunk>> bins;
-  std::map<uint32_t, uint64_t> loffset;        // CSI: virtual offset of the first record that overlaps the bin's first 16 kb window (fill_linear)
-  std::vector<uint64_t> linear;                // 16 kb windows -> virtual offset of the first record overlapping the window
-  uint64_t off_beg = ~0ull, off_end = 0, n_mapped = 0;
-  uint32_t last_bin = ~0u;
-};
+using Chunk = TbiChunk;
+using RefIndex = TbiRef;
 
 struct BgzfReader {
   FILE* f = nullptr;
@@ -134,6 +129,80 @@ void write_bgzf(const std::string& path, const std::string& bytes) {
 
 }  // namespace
 
+// the serialising half of both .tbi builders: fill_linear, the byte layout of the tabix specification, BGZF
+void write_tbi_index(const std::string& tbi_path, const std::vector<std::string>& names, std::vector<TbiRef>& refs) {
+  fill_linear(refs);
+  refs.resize(names.size());
+  std::string o;
+  o.append("TBI\1", 4);
+  put<int32_t>(o, (int32_t)names.size());
+  put<int32_t>(o, 2);                                                 // format: VCF
+  put<int32_t>(o, 1); put<int32_t>(o, 2); put<int32_t>(o, 0);        // col_seq, col_beg, col_end
+  put<int32_t>(o, '#'); put<int32_t>(o, 0);                           // meta, skip
+  std::string nm;
+  for (const std::string& n : names) { nm += n; nm.push_back('\0'); }
+  put<int32_t>(o, (int32_t)nm.size());
+  o += nm;
+  for (const RefIndex& r : refs) {
+    put<int32_t>(o, (int32_t)r.bins.size() + (r.n_mapped ? 1 : 0));
+    for (const auto& b : r.bins) {
+      put<uint32_t>(o, b.first); put<int32_t>(o, (int32_t)b.second.size());
+      for (const Chunk& c : b.second) { put<uint64_t>(o, c.beg); put<uint64_t>(o, c.end); }
+    }
+    if (r.n_mapped) { put<uint32_t>(o, kMetaBin); put<int32_t>(o, 2); put<uint64_t>(o, r.off_beg); put<uint64_t>(o, r.off_end); put<uint64_t>(o, r.n_mapped); put<uint64_t>(o, 0); }
+    put<int32_t>(o, (int32_t)r.linear.size());
+    for (uint64_t v : r.linear) put<uint64_t>(o, v);
+  }
+  put<uint64_t>(o, 0);                                                // n_no_coor
+  write_bgzf(tbi_path, o);
+}
+
+std::string tbi_record_error(uint32_t bits, const std::string& path, int64_t line) {
+  const std::string where = " (" + path + " line " + std::to_string(line) + ")";
+  if (bits & gdbidx::IDX_ERR_POS_LOW) return "index: a record with a POS below 1 is not indexed" + where;
+  return "index: a record with a POS or an END at or above 2^31 is not indexed" + where;
+}
+uint32_t TbiBatchMerger::id_of(const std::string& chrom) {
+  auto it = name_id.find(chrom);
+  if (it != name_id.end()) return (uint32_t)it->second;
+  const int tid = (int)names.size();
+  name_id[chrom] = tid;
+  names.push_back(chrom);
+  refs.resize(names.size());
+  return (uint32_t)tid;
+}
+void TbiBatchMerger::add_chunks(const gdbidx::IdxChunk* chunks, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const gdbidx::IdxChunk& c = chunks[i];
+    if (c.tid >= refs.size()) throw std::runtime_error("index: a chunk of a contig without a name");
+    TbiRef& r = refs[c.tid];
+    std::vector<Chunk>& ch = r.bins[c.bin];
+    if ((c.flags & gdbidx::IDX_CHUNK_FIRST) && r.last_bin == c.bin && !ch.empty()) ch.back().end = c.end;
+    else ch.push_back(Chunk{c.beg, c.end});
+    r.off_beg = std::min(r.off_beg, c.beg);
+    if (c.end == kPendingVoff) { pending_tid = (int)c.tid; pending_bin = c.bin; }
+    else r.off_end = std::max(r.off_end, c.end);
+    r.n_mapped += c.count;
+  }
+  for (size_t i = 0; i < n; ++i) if (chunks[i].flags & gdbidx::IDX_CHUNK_LAST) refs[chunks[i].tid].last_bin = chunks[i].bin;
+}
+void TbiBatchMerger::resolve_pending(uint64_t voff) {
+  if (pending_tid < 0) return;
+  TbiRef& r = refs[(size_t)pending_tid];
+  r.bins[pending_bin].back().end = voff;
+  r.off_end = std::max(r.off_end, voff);
+  pending_tid = -1;
+}
+void TbiBatchMerger::add_windows(uint32_t tid, const uint64_t* minima, size_t n) {
+  if (tid >= refs.size()) throw std::runtime_error("index: windows of a contig without a name");
+  std::vector<uint64_t>& lin = refs[tid].linear;
+  if (lin.size() < n) lin.resize(n, 0);
+  for (size_t w = 0; w < n; ++w) if (minima[w] != ~0ull && (lin[w] == 0 || minima[w] < lin[w])) lin[w] = minima[w];
+}
+uint64_t TbiBatchMerger::num_bins() const { uint64_t n = 0; for (const TbiRef& r : refs) n += r.bins.size(); return n; }
+uint64_t TbiBatchMerger::num_chunks() const { uint64_t n = 0; for (const TbiRef& r : refs) for (const auto& b : r.bins) n += b.second.size(); return n; }
+uint64_t TbiBatchMerger::num_windows() const { uint64_t n = 0; for (const TbiRef& r : refs) n += r.linear.size(); return n; }
+
 void build_tbi_index(const std::string& path) {
   BgzfReader in(path);
   std::vector<RefIndex> refs;
@@ -171,30 +240,7 @@ void build_tbi_index(const std::string& path) {
     if (it == name_id.end()) { tid = (int)names.size(); name_id[chrom] = tid; names.push_back(chrom); } else tid = it->second;
     note_record(refs, tid, pos - 1, end, vbeg, vend);
   }
-  fill_linear(refs);
-  refs.resize(names.size());
-  std::string o;
-  o.append("TBI\1", 4);
-  put<int32_t>(o, (int32_t)names.size());
-  put<int32_t>(o, 2);                                                 // format: VCF
-  put<int32_t>(o, 1); put<int32_t>(o, 2); put<int32_t>(o, 0);        // col_seq, col_beg, col_end
-  put<int32_t>(o, '#'); put<int32_t>(o, 0);                           // meta, skip
-  std::string nm;
-  for (const std::string& n : names) { nm += n; nm.push_back('\0'); }
-  put<int32_t>(o, (int32_t)nm.size());
-  o += nm;
-  for (const RefIndex& r : refs) {
-    put<int32_t>(o, (int32_t)r.bins.size() + (r.n_mapped ? 1 : 0));
-    for (const auto& b : r.bins) {
-      put<uint32_t>(o, b.first); put<int32_t>(o, (int32_t)b.second.size());
-      for (const Chunk& c : b.second) { put<uint64_t>(o, c.beg); put<uint64_t>(o, c.end); }
-    }
-    if (r.n_mapped) { put<uint32_t>(o, kMetaBin); put<int32_t>(o, 2); put<uint64_t>(o, r.off_beg); put<uint64_t>(o, r.off_end); put<uint64_t>(o, r.n_mapped); put<uint64_t>(o, 0); }
-    put<int32_t>(o, (int32_t)r.linear.size());
-    for (uint64_t v : r.linear) put<uint64_t>(o, v);
-  }
-  put<uint64_t>(o, 0);                                                // n_no_coor
-  write_bgzf(path + ".tbi", o);
+  write_tbi_index(path + ".tbi", names, refs);
 }
 
 void build_csi_index(const std::string& path) {

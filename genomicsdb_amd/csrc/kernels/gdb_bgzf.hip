@@ -35,8 +35,6 @@
 
 namespace genomicsdb_amd {
 
-const unsigned char kBgzfEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
 #define BGZF_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) throw std::runtime_error(std::string("BGZF: ") + #expr + " failed: " + hipGetErrorString(_e)); } while (0)
 
 namespace {
@@ -903,33 +901,6 @@ uint32_t bgzf_block_input() {
 // pages of VCF text through the anchored kernel (k_bgzf_deflate_text, 8 KiB blocks only); GDBAMD_BGZF_TEXT=0: the byte-level kernel for everything (A/B runs)
 static bool bgzf_text_kernel() { static const bool v = []() { const char* e = getenv("GDBAMD_BGZF_TEXT"); return !(e && *e == '0'); }(); return v; }
 static int bgzf_waves_per_block() { static const int v = []() { const char* e = getenv("GDBAMD_BGZF_WAVES"); return e && *e == '1' ? 1 : 2; }(); return v; }
-
-std::string bgzf_compress_host(const std::string& bytes) {
-  std::string out;
-  const size_t kHostBlock = 0xff00;                            // htslib's BGZF_BLOCK_SIZE
-  for (size_t at = 0; at < bytes.size(); at += kHostBlock) {
-    const size_t n = std::min<size_t>(kHostBlock, bytes.size() - at);
-    z_stream zs;
-    memset(&zs, 0, sizeof(zs));
-    if (deflateInit2(&zs, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw std::runtime_error("BGZF: deflateInit2 failed");
-    std::vector<unsigned char> buf(deflateBound(&zs, (uLong)n) + 16);
-    zs.next_in = (Bytef*)bytes.data() + at; zs.avail_in = (uInt)n;
-    zs.next_out = buf.data(); zs.avail_out = (uInt)buf.size();
-    const int rc = deflate(&zs, Z_FINISH);
-    const size_t c = buf.size() - zs.avail_out;
-    deflateEnd(&zs);
-    if (rc != Z_STREAM_END) throw std::runtime_error("BGZF: deflate failed");
-    const uint32_t bs = (uint32_t)(c + kBgzfHeaderBytes + kBgzfTrailerBytes - 1);
-    if (bs > 0xFFFFu) throw std::runtime_error("BGZF: block too large");
-    const unsigned char hdr[18] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, (unsigned char)(bs & 0xFFu), (unsigned char)(bs >> 8)};
-    out.append((const char*)hdr, 18);
-    out.append((const char*)buf.data(), c);
-    const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)bytes.data() + at, (uInt)n), isize = (uint32_t)n;
-    out.append((const char*)&crc, 4);
-    out.append((const char*)&isize, 4);
-  }
-  return out;
-}
 
 struct BgzfDeviceCompressor::Impl {
   uint32_t* d_slice = nullptr; uint32_t* d_shift = nullptr; uint32_t* d_shift256 = nullptr; uint32_t block = 0;

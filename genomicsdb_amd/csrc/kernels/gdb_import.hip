@@ -328,6 +328,30 @@ void launch_sorted_sizes(const uint32_t* idx, const uint32_t* size, uint64_t kep
 void launch_gather(const uint32_t* idx, const uint64_t* src, const uint32_t* size, const uint64_t* off, uint64_t kept, uint8_t* out, uint64_t out_bytes, hipStream_t s) {
   if (kept) hipLaunchKernelGGL(k_imp_gather, dim3(grid_for(kept * 64)), dim3(kBlock), 0, s, idx, src, size, off, kept, out, out_bytes);
 }
+// the index pass of a batch, also for the translation units that index text of their own (kernels/gdb_index.hip)
+void index_lines(const char* text, uint32_t n, DBuf<uint64_t>& tile, DBuf<uint64_t>& tile_scan, DBuf<char>& scan_tmp, DBuf<uint32_t>& nl, DBuf<uint32_t>& first_tab,
+                 DBuf<uint32_t>& tab, hipStream_t stream, uint32_t* n_lines_out, uint32_t* n_tabs_out) {
+  const uint32_t n_tiles = (n + kTile - 1u) / kTile;
+  tile.ensure((size_t)n_tiles + 1);
+  tile_scan.ensure((size_t)n_tiles + 1);
+  IMP_HIP_CHECK(hipMemsetAsync(tile.p + n_tiles, 0, sizeof(uint64_t), stream));
+  hipLaunchKernelGGL(k_imp_count, dim3(n_tiles), dim3(kBlock), 0, stream, text, n, tile.p);
+  size_t bytes = 0;
+  IMP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, (const uint64_t*)tile.p, tile_scan.p, (uint64_t)0, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), stream));
+  scan_tmp.ensure(std::max<size_t>(bytes, 16));
+  IMP_HIP_CHECK(rocprim::exclusive_scan((void*)scan_tmp.p, bytes, (const uint64_t*)tile.p, tile_scan.p, (uint64_t)0, (size_t)n_tiles + 1, rocprim::plus<uint64_t>(), stream));
+  uint64_t totals = 0;
+  IMP_HIP_CHECK(hipMemcpyAsync(&totals, tile_scan.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  IMP_HIP_CHECK(hipStreamSynchronize(stream));
+  const uint32_t n_lines = (uint32_t)(totals >> 32), n_tabs = (uint32_t)totals;
+  *n_lines_out = n_lines; *n_tabs_out = n_tabs;
+  if (n_lines == 0) return;
+  nl.ensure(n_lines);
+  first_tab.ensure((size_t)n_lines + 1);
+  tab.ensure(std::max<uint32_t>(n_tabs, 1));
+  IMP_HIP_CHECK(hipMemsetAsync(first_tab.p, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(k_imp_scatter, dim3(n_tiles), dim3(kBlock), 0, stream, text, n, (const uint64_t*)tile_scan.p, nl.p, first_tab.p, tab.p, n_lines, n_tabs);
+}
 }  // namespace impdev
 
 DeviceImporter::DeviceImporter(int device, const VidMapper& vid, const ImportOptions& opt, uint64_t text_budget_bytes, int inflate_mode, const ImportTextTap* tap)
@@ -717,24 +741,10 @@ uint32_t DeviceImporter::Impl::batch(const ImportFile& file, const ImportHeader&
   };
 
   // ---- index
-  const uint32_t n_tiles = (n + kTile - 1u) / kTile;
-  d_tile.ensure((size_t)n_tiles + 1);
-  d_tile_scan.ensure((size_t)n_tiles + 1);
   IMP_HIP_CHECK(hipEventRecord(ev[0], stream));
-  IMP_HIP_CHECK(hipMemsetAsync(d_tile.p + n_tiles, 0, sizeof(uint64_t), stream));
-  hipLaunchKernelGGL(k_imp_count, dim3(n_tiles), dim3(kBlock), 0, stream, (const char*)d_text.p, n, d_tile.p);
-  scan<uint64_t>(d_tile.p, d_tile_scan.p, (size_t)n_tiles + 1);
-  uint64_t totals = 0;
-  IMP_HIP_CHECK(hipMemcpyAsync(&totals, d_tile_scan.p + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-  IMP_HIP_CHECK(hipStreamSynchronize(stream));
-  const uint32_t n_lines = (uint32_t)(totals >> 32), n_tabs = (uint32_t)totals;     // (the text ends with a newline)
+  uint32_t n_lines = 0, n_tabs = 0;
+  index_lines(d_text.p, n, d_tile, d_tile_scan, d_tmp, d_nl, d_first_tab, d_tab, stream, &n_lines, &n_tabs);     // (the text ends with a newline)
   if (n_lines == 0) return 0;
-  d_nl.ensure(n_lines);
-  d_first_tab.ensure((size_t)n_lines + 1);
-  d_tab.ensure(std::max<uint32_t>(n_tabs, 1));
-  IMP_HIP_CHECK(hipMemsetAsync(d_first_tab.p, 0, sizeof(uint32_t), stream));
-  hipLaunchKernelGGL(k_imp_scatter, dim3(n_tiles), dim3(kBlock), 0, stream, (const char*)d_text.p, n, (const uint64_t*)d_tile_scan.p, d_nl.p, d_first_tab.p, d_tab.p,
-                     n_lines, n_tabs);
   IMP_HIP_CHECK(hipEventRecord(ev[1], stream));
 
   const ImpTables T = tables(hdr.n_samples);

@@ -59,6 +59,13 @@ template <class T> struct DBuf {       // grow-only device block
 };
 template <class T> T* dalloc(size_t n) { T* p = nullptr; IMP_HIP_CHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); return p; }
 
+// The importer's newline / tab index pass (defined in gdb_import.hip: k_imp_count, an exclusive scan of the tile counts, k_imp_scatter)
+// over n bytes of text that begin 16-byte aligned and have kTextPad bytes allocated behind them: nl[l] = position of the l-th
+// newline, tab[] = positions of the tabs, first_tab[l] = tabs in front of line l (n_lines + 1 entries).  Waits for the stream once,
+// between the scan and the scatter, for the two totals; the scatter is queued when it returns.  No newline: nothing is scattered.
+void index_lines(const char* text, uint32_t n, DBuf<uint64_t>& tile, DBuf<uint64_t>& tile_scan, DBuf<char>& scan_tmp, DBuf<uint32_t>& nl, DBuf<uint32_t>& first_tab,
+                 DBuf<uint32_t>& tab, hipStream_t stream, uint32_t* n_lines, uint32_t* n_tabs);
+
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 

@@ -10,7 +10,9 @@
 //   compact   per produced partition that the batch touches: k_split_select (length or 0 per line), rocPRIM exclusive scan,
 //             k_split_gather: one wavefront per selected line copies it behind the partition's packed text with aligned 16-byte stores
 //   compress  a partition's packed text accumulates on the device and leaves it as BGZF blocks (BgzfDeviceCompressor, text mode)
-// The '#' lines go through bgzf_compress_host once per output, kBgzfEofBlock ends it, host/vcf_index.h writes <output>.tbi.  An output
+// The '#' lines go through bgzf_compress_host once per output, kBgzfEofBlock ends it, host/vcf_index.h writes <output>.tbi - or, with
+// index_on_device, kernels/gdb_index.h builds it while the output is written: every deflated piece of packed text is a batch of the
+// index, taken while the text is still in device memory, with the blocks it just became as the member table.  An output
 // is written under a temporary name and renamed when its whole input went through: on an error no output of that input is left.
 #pragma once
 #include <cstdint>
@@ -32,6 +34,7 @@ struct SplitStats {
   float ms_index = 0, ms_classify = 0, ms_scan_gather = 0, ms_deflate = 0;      // HIP-event time per phase, summed
   double s_read = 0, s_h2d = 0, s_d2h_write = 0, s_index_build = 0, s_total = 0;      // wall clock: file read (+ host inflate), uploads, compressed download + write, .tbi, all
   float ms_inflate = 0;                        // HIP-event time of the BGZF inflate kernel (BGZF input)
+  double ms_index_kernels = 0;                 // HIP-event time of the index kernels (index_on_device; s_index_build is the wall clock on either path)
 };
 
 struct SplitRequest {
@@ -41,6 +44,9 @@ struct SplitRequest {
   std::string single_output;                                // output path of the only input (one input, one produced partition), else empty
   std::vector<std::string> extra_paths;                     // inputs that the callset mapping does not list
   int device = 0; uint64_t text_budget_bytes = 0; int inflate_mode = 0;      // as for DeviceImporter
+  // the outputs' .tbi by kernels/gdb_index.h while they are written: from the packed text still in device memory, the blocks the deflate
+  // just made and the header member; false: host/vcf_index.h re-reads each finished output.  The files are the same, byte for byte
+  bool index_on_device = false;
 };
 
 struct SplitOutput { std::string original; int partition = 0; std::string path; };

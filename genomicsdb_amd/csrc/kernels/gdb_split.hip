@@ -16,6 +16,8 @@
 #include "gdb_bgzf.h"
 #include "gdb_import.h"
 #include "gdb_import_device.hpp"
+#include "gdb_index.h"
+#include "gdb_inflate.h"
 
 namespace genomicsdb_amd {
 
@@ -122,6 +124,9 @@ struct PartOut {
   std::string final_path, tmp_path;
   FILE* f = nullptr;
   DBuf<char>* acc = nullptr; uint64_t fill = 0;      // the packed text it has collected (Splitter::accs: kept from file to file)
+  // index_on_device: the output so far, in uncompressed and in file bytes, the lines of its header, and its index builder
+  uint64_t u_done = 0, file_pos = 0; int64_t header_lines = 0;
+  size_t slot = 0; bool tbi_begun = false;      // Splitter::tbis[slot]
 };
 
 void remove_quietly(const std::string& path) { if (!path.empty()) (void)remove(path.c_str()); }
@@ -142,6 +147,8 @@ struct Splitter {
   DBuf<unsigned int> d_counters;
   DBuf<char> d_tmp, d_z;
   std::vector<std::unique_ptr<DBuf<char>>> accs;      // one per produced partition
+  std::vector<std::unique_ptr<DeviceTbiBuilder>> tbis;      // index_on_device: the same (the device buffers are kept from file to file)
+  std::vector<BgzfMember> blocks;
   std::vector<char> h_z;
   std::vector<PartOut> outs;                   // of the input that is being read
   std::string original;                        // its name
@@ -178,6 +185,8 @@ struct Splitter {
       o.partition = produce[i];
       if (accs.size() <= i) accs.emplace_back(new DBuf<char>());
       o.acc = accs[i].get();
+      if (tbis.size() <= i) tbis.resize(i + 1);
+      o.slot = i;
       o.sorted_at = (uint32_t)(std::find(sorted_to_index.begin(), sorted_to_index.end(), produce[i]) - sorted_to_index.begin());
       o.final_path = !req.single_output.empty() ? req.single_output : vid.get_split_file_path(name, req.results_directory, o.partition, path);
       o.tmp_path = o.final_path + ".split.tmp";
@@ -203,7 +212,36 @@ struct Splitter {
     st.text_bytes_in += head.size();
     if (lines.empty()) return;
     const std::string z = bgzf_compress_host(lines);
-    for (PartOut& o : outs) { write(o, z.data(), z.size()); st.text_bytes_out += lines.size(); }
+    const int64_t n_lines = (int64_t)std::count(lines.begin(), lines.end(), '\n');
+    for (PartOut& o : outs) {
+      write(o, z.data(), z.size()); st.text_bytes_out += lines.size();
+      o.u_done += lines.size(); o.file_pos += z.size(); o.header_lines += n_lines;
+    }
+  }
+
+  // index_on_device: the output's builder, made when the first block of the first output is there and then kept
+  DeviceTbiBuilder& builder_of(PartOut& o) {
+    std::unique_ptr<DeviceTbiBuilder>& b = tbis.at(o.slot);
+    if (!b) b.reset(new DeviceTbiBuilder(o.tmp_path, (void*)stream));
+    if (!o.tbi_begun) { b->reset(o.tmp_path, o.header_lines); o.tbi_begun = true; }
+    return *b;
+  }
+  // the packed text that flush() just deflated is still in o.acc, the blocks it became are in h_z: a batch of the output's index.
+  // What lies behind the batch's last line is the next block, which is not written yet: its offset is named with the next
+  // batch, or in end_file
+  void index_flushed(PartOut& o, uint64_t n_compressed) {
+    const double t0 = now_s();
+    DeviceTbiBuilder& B = builder_of(o);
+    B.resolve_pending(o.file_pos << 16);
+    uint64_t total = 0, break_at = 0;
+    if (!bgzf_walk((const uint8_t*)h_z.data(), n_compressed, blocks, &total, &break_at) || total != o.fill)
+      throw GenomicsDBDeviceException("split: the deflated blocks of " + o.tmp_path + " are not the text they were made of");
+    IndexMemberTable table;
+    for (const BgzfMember& m : blocks) if (m.isize) { table.ubase.push_back(o.u_done + m.out_off); table.coff.push_back(o.file_pos + m.offset); }
+    table.total = o.u_done + o.fill; table.v_total = DeviceTbiBuilder::kPending;
+    B.set_members(table);
+    if (B.add_batch(o.acc->p, (uint32_t)o.fill, o.u_done) != o.fill) throw GenomicsDBDeviceException("split: the packed text of " + o.tmp_path + " does not end with a line");
+    st.s_index_build += now_s() - t0;
   }
 
   template <class T> void scan(const T* in, T* out, size_t n) {
@@ -226,6 +264,8 @@ struct Splitter {
     write(o, h_z.data(), (size_t)n);
     st.s_d2h_write += now_s() - t0;
     st.text_bytes_out += o.fill;
+    if (req.index_on_device) index_flushed(o, n);
+    o.u_done += o.fill; o.file_pos += n;
     o.fill = 0;
   }
 
@@ -291,8 +331,9 @@ struct Splitter {
       IMP_HIP_CHECK(hipStreamSynchronize(stream));
       IMP_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1])); st.ms_scan_gather += ms;
       if (!total) continue;
-      if (o.fill + total > o.acc->cap) flush(o);
-      o.acc->ensure((size_t)std::max<uint64_t>(chunk, (uint64_t)total));      // (grows only when empty: flush() came first)
+      const uint64_t pad = req.index_on_device ? kTextPad : 0u;      // (the index pass reads whole 16-byte groups)
+      if (o.fill + total + pad > o.acc->cap) flush(o);
+      o.acc->ensure((size_t)(std::max<uint64_t>(chunk, (uint64_t)total) + pad));      // (grows only when empty: flush() came first)
       IMP_HIP_CHECK(hipEventRecord(ev[2], stream));
       hipLaunchKernelGGL(k_split_gather, dim3(grid_for((uint64_t)n_lines * 64u)), dim3(kBlock), 0, stream, b.d_text, b.n_bytes, b.d_nl, (const uint32_t*)d_sel.p,
                          (const uint32_t*)d_off.p, n_lines, o.acc->p + o.fill, (uint64_t)o.acc->cap - o.fill);
@@ -314,7 +355,12 @@ struct Splitter {
       o.f = nullptr;
       if (rc != 0) throw VCF2BinaryException("cannot write " + o.tmp_path);
       const double t0 = now_s();
-      build_tbi_index(o.tmp_path);
+      if (req.index_on_device) {
+        DeviceTbiBuilder& B = builder_of(o);
+        B.resolve_pending((o.file_pos + sizeof(kBgzfEofBlock)) << 16);      // behind the last line: the end of the file
+        B.finish(o.tmp_path + ".tbi");
+        st.ms_index_kernels += B.st.ms_index + B.st.ms_records + B.st.ms_chunks + B.st.ms_linear;
+      } else build_tbi_index(o.tmp_path);
       st.s_index_build += now_s() - t0;
     }
     for (PartOut& o : outs) {
@@ -386,6 +432,7 @@ std::vector<SplitOutput> split_files_device(const VidMapper& vid, const SplitReq
   opt.file_root = req.file_root;
   {
     DeviceImporter imp(req.device, vid, opt, req.text_budget_bytes, req.inflate_mode, &tap);
+    struct DropBuilders { Splitter& s; ~DropBuilders() { s.tbis.clear(); } } drop{S};      // (they wait on the importer's stream: gone before it is)
     for (const auto& f : files) {
       try {
         S.begin_file(f.first, f.second);

@@ -16,13 +16,14 @@
 // "produce_combined_vcf" in the same run combines the cells of the batch only, like the reference's in-line operator.
 // Splitting (reference tools/src/vcf2tiledb.cc:118-151; nothing is imported):
 //   vcf2tiledb [-r <rank>] --split-files [--split-all-partitions] [--split-files-results-directory <dir>] [--split-output-filename <file>]
-//              [--split-callset-mapping-file] <loader.json> [more VCF files ..]
+//              [--split-callset-mapping-file] [--split-index-on-device] <loader.json> [more VCF files ..]
 // cuts every (g)VCF text file of the callset mapping, and the files named behind the loader JSON, into one bgzipped and tabix-indexed
 // file per column partition on the rank's GPU (kernels/gdb_split.hip): partition `rank`, or all of them in one pass per file with
 // --split-all-partitions.  Outputs are <dir, or the input's directory>/partition_<p>_<basename> unless the callset mapping's
 // "split_files_paths" or --split-output-filename (one input, one partition) names them.  --split-callset-mapping-file also writes,
 // per produced partition, the callset mapping that names the split files and a loader JSON that names those mappings, by the same
-// path rule.  With "row_based_partitioning": true the reference's message is printed and nothing is done.
+// path rule.  --split-index-on-device builds each output's .tbi on the GPU while the output is written (kernels/gdb_index.hip) instead
+// of re-reading the finished file on the host; the files are the same.  With "row_based_partitioning": true the reference's message is printed and nothing is done.
 #include <getopt.h>
 #include <sys/stat.h>
 
@@ -55,7 +56,7 @@ static void write_text_file(const std::string& path, const std::string& text, co
 
 // --split-files: see the head of this file
 static int split_files_main(const std::string& loader_json, int rank, bool all_partitions, const std::string& results_directory, const std::string& output_filename,
-                            bool write_mappings, bool inflate_on_host, const std::vector<std::string>& extra_paths) {
+                            bool write_mappings, bool inflate_on_host, bool index_on_device, const std::vector<std::string>& extra_paths) {
   const mini_json::Value doc = mini_json::parse_file(loader_json);
   if (doc.HasMember("row_based_partitioning") && doc["row_based_partitioning"].GetBool()) {
     std::cerr << "Splitting is available for column partitioning, row partitioning should be trivial if samples are scattered across files. See wiki page "
@@ -75,6 +76,7 @@ static int split_files_main(const std::string& loader_json, int rank, bool all_p
   req.results_directory = results_directory;
   req.extra_paths = extra_paths;
   req.inflate_mode = inflate_on_host ? 1 : 0;
+  req.index_on_device = index_on_device;
   if (const char* e = getenv("GDBAMD_DEVICE")) req.device = atoi(e); else if (const char* e2 = getenv("LOCAL_RANK")) req.device = atoi(e2);
   if (const char* e = getenv("GDBAMD_SPLIT_TEXT_BUDGET")) req.text_budget_bytes = strtoull(e, nullptr, 10);
   const std::vector<std::pair<std::string, std::string>> inputs = split_input_files(vid, req);
@@ -86,7 +88,7 @@ static int split_files_main(const std::string& loader_json, int rank, bool all_p
             << ",lines_written," << st.num_lines_written << ",text_bytes_in," << st.text_bytes_in << ",text_bytes_out," << st.text_bytes_out << ",compressed_bytes_out,"
             << st.compressed_bytes_out << ",batches," << st.num_batches << ",index_ms," << st.ms_index << ",classify_ms," << st.ms_classify << ",scan_gather_ms,"
             << st.ms_scan_gather << ",deflate_ms," << st.ms_deflate << ",inflate_ms," << st.ms_inflate << ",read_s," << st.s_read << ",h2d_s," << st.s_h2d
-            << ",d2h_write_s," << st.s_d2h_write << ",index_build_s," << st.s_index_build << "\n";
+            << ",d2h_write_s," << st.s_d2h_write << ",index_build_s," << st.s_index_build << ",index_kernels_ms," << st.ms_index_kernels << "\n";
   if (!write_mappings) return 0;
   // the callset mapping of a partition (reference vid_mapper.cc:1083-1151): every callset with its row, its index in the file and the split file
   auto split_path_of = [&](const std::string& original, int p) {
@@ -122,14 +124,16 @@ static int split_files_main(const std::string& loader_json, int rank, bool all_p
 }
 
 int main(int argc, char** argv) {
-  enum { ARG_VERSION = 1000, ARG_IMPORT_ON_DEVICE, ARG_INFLATE_ON_HOST, ARG_SPLIT_FILES, ARG_SPLIT_ALL, ARG_SPLIT_DIRECTORY, ARG_SPLIT_OUTPUT, ARG_SPLIT_MAPPING };
+  enum { ARG_VERSION = 1000, ARG_IMPORT_ON_DEVICE, ARG_INFLATE_ON_HOST, ARG_SPLIT_FILES, ARG_SPLIT_ALL, ARG_SPLIT_DIRECTORY, ARG_SPLIT_OUTPUT, ARG_SPLIT_MAPPING, ARG_SPLIT_INDEX_ON_DEVICE };
   static struct option long_options[] = {{"tmp-directory", 1, 0, 'T'}, {"rank", 1, 0, 'r'}, {"version", 0, 0, ARG_VERSION}, {"import-on-device", 0, 0, ARG_IMPORT_ON_DEVICE},
                                          {"inflate-on-host", 0, 0, ARG_INFLATE_ON_HOST},
                                          {"split-files", 0, 0, ARG_SPLIT_FILES}, {"split-all-partitions", 0, 0, ARG_SPLIT_ALL},
                                          {"split-files-results-directory", 1, 0, ARG_SPLIT_DIRECTORY}, {"split-output-filename", 1, 0, ARG_SPLIT_OUTPUT},
-                                         {"split-callset-mapping-file", 0, 0, ARG_SPLIT_MAPPING}, {0, 0, 0, 0}};
+                                         {"split-callset-mapping-file", 0, 0, ARG_SPLIT_MAPPING}, {"split-index-on-device", 0, 0, ARG_SPLIT_INDEX_ON_DEVICE},
+                                         {0, 0, 0, 0}};
   int rank = launcher_rank();
   bool import_on_device = false, inflate_on_host = false;
+  bool split_index_on_device = false;
   bool split_files = false, split_all = false, split_mapping = false;      // (any of the five split options turns splitting on; the reference needs --split-files next to the others)
   std::string split_directory, split_output;
   int c;
@@ -145,6 +149,7 @@ int main(int argc, char** argv) {
       case ARG_SPLIT_DIRECTORY: split_files = true; split_directory = optarg; break;
       case ARG_SPLIT_OUTPUT: split_files = true; split_output = optarg; break;
       case ARG_SPLIT_MAPPING: split_files = true; split_mapping = true; break;
+      case ARG_SPLIT_INDEX_ON_DEVICE: split_files = true; split_index_on_device = true; break;
       default: std::cerr << "Unknown command line argument\n"; return -1;
     }
   }
@@ -152,7 +157,7 @@ int main(int argc, char** argv) {
   const std::string loader_json = argv[optind];
   if (split_files) {
     try {
-      return split_files_main(loader_json, rank, split_all, split_directory, split_output, split_mapping, inflate_on_host,
+      return split_files_main(loader_json, rank, split_all, split_directory, split_output, split_mapping, inflate_on_host, split_index_on_device,
                               std::vector<std::string>(argv + optind + 1, argv + argc));
     } catch (const std::exception& e) {
       std::cerr << "vcf2tiledb: " << e.what() << "\n";

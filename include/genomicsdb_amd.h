@@ -383,6 +383,30 @@ int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nb
 int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
                               const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
                               uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs);
+/* The same with the outputs' .tbi built on the device (index_on_device != 0; kernels/gdb_index.hip): each output is indexed while it is written, from its
+ * packed text that is still in device memory, the sizes of the blocks the deflate just made and the header member written on the host; the finished file is
+ * not read again.  The files are those of index_on_device == 0, byte for byte.  stats as above (11..15: .tbi build is the wall clock of index building on
+ * either path) plus 17 HIP-event ms of the index kernels (0 with the host builder). */
+#define GDBAMD_SPLIT_INDEX_NUM_STATS 18
+int gdbamd_split_files_device_index(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
+                                    const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
+                                    uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs,
+                                    int index_on_device);
+/* <path>.tbi of a bgzipped VCF, built on GPU `device` (kernels/gdb_index.hip): the file gdbamd_build_output_index(path, 0) writes, byte for byte.  The file
+ * crosses the link compressed and is inflated on the device in batches of whole lines of about text_budget_bytes (0: 64 MiB); per batch the device finds the
+ * record lines, their intervals, bins, virtual offsets, chunks and the minima of the 16 kb windows, the host joins the batches, lays the index out and
+ * compresses it.  Written through a temporary name: after an error no .tbi exists.  Refused: a file that is not a BGZF chain from its first byte to its last
+ * (with the byte offset where the chain breaks), a member with a bad stream, ISIZE or CRC32, a record with POS < 1 or POS / END >= 2^31 (file and 1-based
+ * line).  stats may be NULL. */
+typedef struct gdbamd_index_stats {
+  int64_t members, batches, lines, records;     /* BGZF members; batches; lines; record lines */
+  int64_t contigs, bins, chunks, linear_windows; /* of the index as written (bins without the meta bin) */
+  uint64_t text_bytes;                          /* inflated bytes */
+  int64_t atomics;                              /* atomic minima issued on the windows (one per run of records that share a window inside a wavefront) */
+  double ms_inflate, ms_index, ms_records, ms_chunks, ms_linear;  /* HIP-event ms of inflate, line index, select + records, sorts + chunks, windows */
+  double s_read, s_serialize_write, s_total;    /* wall seconds of file read, merge + layout + compress + write, the whole call */
+} gdbamd_index_stats;
+int gdbamd_index_vcf_device(const char* path, int device, uint64_t text_budget_bytes, gdbamd_index_stats* stats);
 /* vcf_histogram on GPU `device` (kernels/gdb_histogram.hip; reference tools/src/vcf_histogram.cc, tiledb_loader.cc:428-456, utils/histogram.cc): one pass
  * over every input file of the callset mapping - (g)VCF text, plain, gzip or BGZF, and BCF2; a file whose name is one of the nstreams `names` is read from
  * memory - counts its records per bin of a uniform histogram over the columns [0, max_histogram_range]:
