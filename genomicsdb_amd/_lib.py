@@ -52,7 +52,7 @@ SYMBOLS = ["gdb_mi355_last_error", "gdb_mi355_device_count", "gdb_mi355_init", "
            "gdbamd_importer_create", "gdbamd_importer_add_buffer_stream", "gdbamd_importer_setup_loader", "gdbamd_importer_stream_file_idx", "gdbamd_importer_write",
            "gdbamd_importer_import_batch", "gdbamd_importer_is_done", "gdbamd_importer_finish", "gdbamd_importer_stats", "gdbamd_importer_destroy",
            "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text", "gdbamd_vcfdiff",
-           "gdbamd_index_vcf_device", "gdbamd_split_files_device_index",
+           "gdbamd_index_vcf_device", "gdbamd_split_files_device_index", "gdbamd_merge_cell_files",
            "gdbamd_engine_columns_select", "gdbamd_engine_page_columns"]
 
 
@@ -190,6 +190,9 @@ def lib():
     L.gdbamd_import_cells_device_rows.argtypes = L.gdbamd_import_cells_device_streams.argtypes + [c.c_int64, c.c_int64]
     L.gdbamd_merge_cells.argtypes = [c.c_int, c.POINTER(c.c_void_p), c.POINTER(c.c_uint64), c.POINTER(c.c_void_p), c.POINTER(c.c_uint64), c.POINTER(c.c_int64), c.c_int,
                                      c.POINTER(c.c_double), c.c_int]
+    L.gdbamd_merge_cell_files.restype = c.c_int64
+    L.gdbamd_merge_cell_files.argtypes = [c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_void_p), c.POINTER(c.c_uint64), c.c_char_p, c.c_int, c.c_uint64,
+                                          c.POINTER(c.c_double), c.c_int]
     L.gdbamd_split_files_device.argtypes = [c.c_char_p, c.c_char_p, c.c_char_p, c.c_int, c.POINTER(c.c_int64), c.POINTER(c.c_int64), c.c_int, c.c_char_p, c.c_char_p, c.c_int,
                                             c.c_uint64, c.c_int, c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_double), c.c_int, c.POINTER(c.c_void_p)]
     L.gdbamd_split_files_device_index.argtypes = L.gdbamd_split_files_device.argtypes + [c.c_int]

@@ -746,6 +746,34 @@ def merge_cells(streams, device=0, stats=None):
         L.gdbamd_free(p)
 
 
+MERGE_FILES_STAT_NAMES = MERGE_STAT_NAMES + ("rounds", "carried_cells", "grown", "window_bytes", "device_bytes_peak", "pinned_bytes", "s_read", "s_write", "s_wait_device")
+
+
+def merge_cell_files(sources, output, device=0, window_bytes=0, stats=None):
+    """merge_cells from files to a file, for arrays larger than device memory: `sources` mixes paths (str: files of begin-cells, read
+    window by window) and bytes; their cells go to the file `output` in (column, row) order, byte for byte what merge_cells gives,
+    through <output>.merge.tmp.  `window_bytes` caps the input cell bytes resident on GPU `device` over all sources (0: derived from
+    the free device memory); device memory is about 8.7 times that, whatever the sources' lengths.  Raises as merge_cells does, with
+    cell indices and byte offsets counted from the start of the source, and then leaves neither file.  Returns the number of cells.
+    `stats`, a dict, receives MERGE_FILES_STAT_NAMES ("rounds", "carried_cells" summed over them, "grown": rounds that had to double
+    a source's share of the window)."""
+    L = _lib.lib()
+    items = [os.fsencode(s) if isinstance(s, (str, os.PathLike)) else bytes(s) for s in sources]
+    is_path = [isinstance(s, (str, os.PathLike)) for s in sources]
+    k = len(items)
+    if k == 0:
+        raise ValueError("merge_cell_files: at least one source")
+    paths = (ctypes.c_char_p * k)(*[v if p else None for v, p in zip(items, is_path)])
+    data = (ctypes.c_void_p * k)(*[None if p else ctypes.cast(ctypes.c_char_p(v), ctypes.c_void_p) for v, p in zip(items, is_path)])      # (items keeps the bytes alive)
+    sizes = (ctypes.c_uint64 * k)(*[0 if p else len(v) for v, p in zip(items, is_path)])
+    st = (ctypes.c_double * len(MERGE_FILES_STAT_NAMES))()
+    n = L.gdbamd_merge_cell_files(k, paths, data, sizes, os.fsencode(output), int(device), int(window_bytes), st, len(MERGE_FILES_STAT_NAMES))
+    _check(n >= 0, "merge_cell_files")
+    if stats is not None:
+        stats.update({name: (float(v) if name[:2] in ("ms", "s_") else int(v)) for name, v in zip(MERGE_FILES_STAT_NAMES, st)})
+    return n
+
+
 def bgzf_compress(data, vcf_text=False):
     """BGZF blocks (no EOF block) of `data`, deflated by the device kernels (kernels/gdb_bgzf.hip); returns (bytes, kernel ms).
     vcf_text: the anchored kernel of the "z" stream (matches begin at tabs / newlines) instead of the byte-level one"""

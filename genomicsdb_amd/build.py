@@ -173,6 +173,15 @@ def build_hostsim_merge():
     return os.path.join(d, "libhostsim_merge.so"), os.path.join(d, "hostsim_merge_main")
 
 
+def build_hostsim_merge_files():
+    """CPU harness of the windowed merge (host/merge_files_common.hpp's planner and round loop over pools in host memory, the bodies
+    of core/gdb_merge.hpp) and the same source as a stand-alone program built with the address and undefined-behaviour sanitizers
+    (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_merge_files")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_merge_files.so"), os.path.join(d, "hostsim_merge_files_main")
+
+
 def build_hostsim_split():
     """The bodies of the device splitter (core/gdb_split.hpp) as a stand-alone program built with the address and
     undefined-behaviour sanitizers (tests only); -> program"""

@@ -612,6 +612,32 @@ int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nb
     return 0;
   } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
 }
+int64_t gdbamd_merge_cell_files(int nsources, const char* const* paths, const void* const* data, const uint64_t* nbytes, const char* output_path, int device,
+                                uint64_t window_bytes, double* stats, int nstats) {
+  try {
+    if (nsources <= 0 || !output_path || !*output_path) throw GenomicsDBConfigException("gdbamd_merge_cell_files: no source or no output path");
+    std::vector<CellSource> sources((size_t)nsources);
+    for (int i = 0; i < nsources; ++i) {
+      CellSource& s = sources[(size_t)i];
+      if (paths && paths[i]) { s.path = paths[i]; if (s.path.empty()) throw GenomicsDBConfigException("gdbamd_merge_cell_files: empty path"); continue; }
+      if (!nbytes || (nbytes[i] && (!data || !data[i]))) throw GenomicsDBConfigException("gdbamd_merge_cell_files: source " + std::to_string(i) + " has neither a path nor data");
+      s.data = data ? data[i] : nullptr; s.nbytes = nbytes[i];
+    }
+    MergeFilesOptions opt;
+    opt.device = device; opt.window_bytes = window_bytes;
+    MergeFilesStats st;
+    const uint64_t cells = merge_cell_files_device(sources, output_path, opt, &st);
+    if (stats && nstats > 0) {
+      const double v[GDBAMD_MERGE_FILES_NUM_STATS] = {(double)st.num_streams, (double)st.cells_in, (double)st.cells_out, (double)st.bytes_out, (double)st.tile,
+                                                      st.ms_keys, st.ms_rank, st.ms_scan, st.ms_gather, st.s_h2d, st.s_d2h, st.s_total,
+                                                      (double)st.rounds, (double)st.carried_cells, (double)st.grown, (double)st.window_bytes, (double)st.device_bytes_peak,
+                                                      (double)st.pinned_bytes, st.s_read, st.s_write, st.s_wait_device};
+      memcpy(stats, v, sizeof(double) * (size_t)std::min<int>(nstats, GDBAMD_MERGE_FILES_NUM_STATS));
+    }
+    g_last_error.clear();
+    return (int64_t)cells;
+  } catch (const std::exception& e) { g_last_error = e.what(); return -1; }
+}
 int gdbamd_split_files_device(const char* vid_mapping_file, const char* callset_mapping_file, const char* file_root, int npartitions, const int64_t* begins,
                               const int64_t* ends, int produce, const char* results_directory, const char* single_output_name, int device,
                               uint64_t text_budget_bytes, int inflate_mode, int nextra, const char* const* extra_paths, double* stats, int nstats, char** outputs) {

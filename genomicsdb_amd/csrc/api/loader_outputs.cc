@@ -51,7 +51,8 @@ void produce_loader_outputs(const LoaderOutputs& out, const mini_json::Value& do
     struct stat have;
     const bool merge = merges(loader, array_file, &have);
     std::vector<uint8_t> merged;
-    if (merge) {      // the batch joins the cells the array holds: on the device, or not at all
+    bool windowed = merge && out.merge_windowed;
+    if (merge && !windowed) {      // the batch joins the cells the array holds: on the device, or not at all
       const auto tm = std::chrono::steady_clock::now();
       std::vector<uint8_t> old((size_t)have.st_size);
       FILE* in = fopen(array_file.c_str(), "rb");
@@ -63,14 +64,47 @@ void produce_loader_outputs(const LoaderOutputs& out, const mini_json::Value& do
       std::vector<CellStream> streams(2);
       streams[0].data = old.data(); streams[0].nbytes = old.size();
       streams[1].data = cells.data(); streams[1].nbytes = cells.size();
-      merged = merge_cell_streams_device(streams, device, &ms);
-      std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",merge_tiledb_array,Wall-clock time(s)," << since(tm)
+      try {
+        merged = merge_cell_streams_device(streams, device, &ms);
+        std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",merge_tiledb_array,Wall-clock time(s)," << since(tm)
+                  << ",streams," << ms.num_streams << ",cells_in," << ms.cells_in << ",cells_out," << ms.cells_out << ",bytes_out," << ms.bytes_out << ",tile," << ms.tile
+                  << ",keys_ms," << ms.ms_keys << ",rank_ms," << ms.ms_rank << ",scan_ms," << ms.ms_scan << ",gather_ms," << ms.ms_gather << ",h2d_s," << ms.s_h2d
+                  << ",d2h_s," << ms.s_d2h << ",merge_s," << ms.s_total << "\n";
+      } catch (const VCF2BinaryException& e) {      // the sizes do not fit the device together: window by window, then
+        if (std::string(e.what()).find("arrays larger than device memory are not merged") == std::string::npos) throw;
+        std::cerr << out.tool << ": " << e.what() << "; merging window by window instead (--merge-window-bytes)\n";
+        windowed = true;
+      }
+    }
+    if (windowed) {      // cells.bin is read as a file, window by window, and never whole; the merge writes the new file itself
+      const auto tm = std::chrono::steady_clock::now();
+      std::vector<CellSource> sources(2);
+      sources[0].path = array_file;
+      sources[1].data = cells.data(); sources[1].nbytes = cells.size();
+      MergeFilesOptions mo;
+      mo.device = device; mo.window_bytes = out.merge_window_bytes;
+      MergeFilesStats ms;
+      merge_cell_files_device(sources, array_file, mo, &ms);
+      std::cerr << "GENOMICSDB_TIMER,Rank," << rank << ",merge_tiledb_array_windowed,Wall-clock time(s)," << since(tm)
                 << ",streams," << ms.num_streams << ",cells_in," << ms.cells_in << ",cells_out," << ms.cells_out << ",bytes_out," << ms.bytes_out << ",tile," << ms.tile
-                << ",keys_ms," << ms.ms_keys << ",rank_ms," << ms.ms_rank << ",scan_ms," << ms.ms_scan << ",gather_ms," << ms.ms_gather << ",h2d_s," << ms.s_h2d
-                << ",d2h_s," << ms.s_d2h << ",merge_s," << ms.s_total << "\n";
+                << ",rounds," << ms.rounds << ",carried_cells," << ms.carried_cells << ",grown," << ms.grown << ",window_bytes," << ms.window_bytes
+                << ",device_bytes_peak," << ms.device_bytes_peak << ",pinned_bytes," << ms.pinned_bytes << ",keys_ms," << ms.ms_keys << ",rank_ms," << ms.ms_rank
+                << ",scan_ms," << ms.ms_scan << ",gather_ms," << ms.ms_gather << ",read_s," << ms.s_read << ",write_s," << ms.s_write << ",wait_device_s," << ms.s_wait_device
+                << ",merge_s," << ms.s_total << "\n";
+      if (!out.spooled_cells_file.empty()) remove(out.spooled_cells_file.c_str());
+      if (wants(doc, "compress_tiledb_array")) {      // (the columnar file is built from the merged cells staged whole)
+        struct stat now;
+        FILE* in = fopen(array_file.c_str(), "rb");
+        if (!in || ::stat(array_file.c_str(), &now) != 0) { if (in) fclose(in); throw GenomicsDBConfigException("cannot read " + array_file); }
+        merged.resize((size_t)now.st_size);
+        const size_t got = merged.empty() ? 0 : fread(merged.data(), 1, merged.size(), in);
+        fclose(in);
+        if (got != merged.size()) throw GenomicsDBConfigException("short read from " + array_file);
+      }
     }
     const std::vector<uint8_t>& array_cells = merge ? merged : cells;
-    if (!merge && !out.spooled_cells_file.empty()) {      // the import wrote these very bytes batch by batch
+    if (windowed) {      // (written above)
+    } else if (!merge && !out.spooled_cells_file.empty()) {      // the import wrote these very bytes batch by batch
       if (rename(out.spooled_cells_file.c_str(), array_file.c_str()) != 0) throw GenomicsDBConfigException("cannot rename " + out.spooled_cells_file + " to " + array_file);
     } else {
       const std::string write_to = merge ? array_file + ".merge.tmp" : array_file;

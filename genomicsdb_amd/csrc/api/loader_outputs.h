@@ -4,7 +4,8 @@
 //                                    there, the cells are MERGED into it on the device (kernels/gdb_merge.hip) through a temporary
 //                                    name in the same directory; "compress_tiledb_array": the columnar fragment file next to it
 //   "produce_combined_vcf": true  -> combined in-line on the GPU and written to stdout
-// The merge, the compressed fragment and the combine take the cells of the import WHOLE, in host memory.
+// The merge, the compressed fragment and the combine take the cells of the import WHOLE, in host memory; the windowed merge
+// (LoaderOutputs::merge_windowed) reads the array it merges into from its file, window by window.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -22,6 +23,11 @@ struct LoaderOutputs {
   // a file in the array's directory that already holds exactly the cells (an import that spooled its batches): renamed to cells.bin
   // instead of written.  Removed when the cells are merged into an existing array
   std::string spooled_cells_file;
+  // vcf2tiledb --merge-window-bytes: a merge into an existing array goes window by window from cells.bin, read as a file, and the
+  // batch in memory to the new cells.bin (merge_cell_files_device), with this many input bytes on the device (0: derived from its free
+  // memory).  Without it the merge runs in-core and turns to the windowed path only when the in-core path refuses the sizes
+  bool merge_windowed = false;
+  uint64_t merge_window_bytes = 0;
 };
 // <workspace>/<array> of the rank, created when missing
 std::string loader_array_directory(const GenomicsDBImportConfig& loader, int rank);

@@ -85,5 +85,20 @@ GDB_HD uint32_t merge_tile_position(const MergeKey* keys, const MergeTile& t, ui
   return (i - t.na) + merge_rank_of_b(keys[i], keys, t.na);
 }
 
+// ---- the windowed merge (merge_cell_files_device): a source's resident cells are cut at the round's watermark, the cells below it
+// are merged and the rest carried to the other pool
+// the cut: how many of the sorted keys K[0, n) lie strictly below `w` - those a round may emit.  Strict, so that a run of keys equal
+// to the watermark is never split between two rounds
+GDB_HD uint64_t merge_cut_below(const MergeKey* K, uint64_t n, const MergeKey& w) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (merge_key_less(K[mid], w)) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+// the order check across a chunk boundary: the first cell of a refill must not come before the source's previous cell
+GDB_HD bool merge_boundary_in_order(const MergeKey& previous, const MergeKey& first_new) { return !merge_key_less(first_new, previous); }
+// the carry: a kept cell at byte `off` of its pool, where the source's kept bytes begin at `kept_from`, lies at this byte of the other
+// pool, where they begin at `kept_to` (the kept cells of a source are contiguous, so they move as one block)
+GDB_HD uint64_t merge_carry_offset(uint64_t off, uint64_t kept_from, uint64_t kept_to) { return off - kept_from + kept_to; }
+
 }  // namespace gdbmerge
 }  // namespace genomicsdb_amd

@@ -103,6 +103,28 @@ struct MergeStats {
 };
 std::vector<uint8_t> merge_cell_streams_device(const std::vector<CellStream>& streams, int device, MergeStats* stats = nullptr);
 
+// The same merge from files to a file, for arrays larger than device memory (kernels/gdb_merge.hip, host/merge_files_common.hpp): the
+// sources - files of begin-cells, read with pread, or memory - are merged round by round through pinned staging and device pools
+// bounded by `window_bytes`, and the output, byte for byte what merge_cell_streams_device gives, is written to <output_path>.merge.tmp
+// and renamed to output_path on success.  A round loads whole cells of every source up to its share of the window, emits the cells
+// strictly below the smallest last-loaded key of the sources not yet exhausted (the watermark) and carries the rest; a round that can
+// emit nothing doubles the share of the sources that hold the watermark (`grown`).  window_bytes caps the input cell bytes resident on
+// the device (carried + fresh, over all sources; growth aside; every source gets the same share of it, but no more than it is long);
+// 0: a sixteenth of the free device memory, at most 64 MiB, the fastest window measured (profiles/device_merge_files.md).  Peak device
+// memory is about 8.7 x window_bytes (two pools, the output buffer, 136 bytes of tables per 24 bytes of pool - the smallest cell) plus
+// the row bitmaps (sources x largest row / 8 bytes); pinned host memory is 4.7 x window_bytes; neither depends on the sources' lengths.
+// Refusals keep the words of the in-core merge; cell indices and byte offsets count from the start of the source.  The shared row
+// named is the smallest one known in the round that first finds one (the in-core merge sees all rows at once and names the smallest
+// of all).  After a refusal neither output_path (when it did not exist) nor the temporary file is left.  Returns the number of cells.
+struct CellSource { std::string path; const void* data = nullptr; uint64_t nbytes = 0; };      // a file when path is not empty, else memory
+struct MergeFilesOptions { int device = 0; uint64_t window_bytes = 0; };
+struct MergeFilesStats : MergeStats {        // (s_h2d, s_d2h stay 0: the transfers overlap the kernels; ms_gather includes the wait for the previous round's download)
+  int64_t rounds = 0, carried_cells = 0, grown = 0;       // carried_cells: summed over the rounds
+  uint64_t window_bytes = 0, device_bytes_peak = 0, pinned_bytes = 0;      // the window as used (after growth: the sum of the shares)
+  double s_read = 0, s_write = 0, s_wait_device = 0;      // wall clock of the host thread: refills, writes, waiting for the device
+};
+uint64_t merge_cell_files_device(const std::vector<CellSource>& sources, const std::string& output_path, const MergeFilesOptions& options, MergeFilesStats* stats = nullptr);
+
 // the importer's number parsers (strtoll / strtod over the whole token, VCF2BinaryException otherwise): the device path runs
 // them on the tokens it deferred
 int64_t import_parse_int(const char* p, size_t n, const std::string& what);

@@ -1,5 +1,5 @@
 // vcf2tiledb - command line of the reference's import tool for what this build implements:
-//   vcf2tiledb [-r <rank>] [--import-on-device [--inflate-on-host]] <loader.json>
+//   vcf2tiledb [-r <rank>] [--import-on-device [--inflate-on-host]] [--merge-window-bytes <N>] <loader.json>
 // (reference: tools/src/vcf2tiledb.cc:54-140; VCF2TileDBLoader::read_all, src/main/cpp/src/loader/tiledb_loader.cc:845-965).
 // The (g)VCFs of the callset mapping are converted to begin-cells of column partition `rank` (host, vcf_importer.cc) and
 //   "produce_tiledb_array": true  -> written to <workspace>/<array>/cells.bin, the array file gt_mpi_gather and the JNI stream open
@@ -13,6 +13,9 @@
 //   "delete_and_create_tiledb_array": false  (written out; the reference's default)
 // a batch is MERGED into an existing <workspace>/<array>/cells.bin on the rank's GPU (kernels/gdb_merge.hip), the result written to a
 // temporary name in the same directory and renamed over cells.bin.  With the key absent or true the array file is overwritten.
+// --merge-window-bytes <N>: the merge goes window by window from the cells.bin file and the batch to the new file, with at most N input
+// bytes on the device (0: derived from its free memory) - for arrays larger than device memory; cells.bin is never read whole.  Without
+// the option the merge runs in-core, and turns to the windowed path, saying so, only when the sizes do not fit the device together.
 // "produce_combined_vcf" in the same run combines the cells of the batch only, like the reference's in-line operator.
 // Splitting (reference tools/src/vcf2tiledb.cc:118-151; nothing is imported):
 //   vcf2tiledb [-r <rank>] --split-files [--split-all-partitions] [--split-files-results-directory <dir>] [--split-output-filename <file>]
@@ -124,9 +127,9 @@ static int split_files_main(const std::string& loader_json, int rank, bool all_p
 }
 
 int main(int argc, char** argv) {
-  enum { ARG_VERSION = 1000, ARG_IMPORT_ON_DEVICE, ARG_INFLATE_ON_HOST, ARG_SPLIT_FILES, ARG_SPLIT_ALL, ARG_SPLIT_DIRECTORY, ARG_SPLIT_OUTPUT, ARG_SPLIT_MAPPING, ARG_SPLIT_INDEX_ON_DEVICE };
+  enum { ARG_VERSION = 1000, ARG_IMPORT_ON_DEVICE, ARG_INFLATE_ON_HOST, ARG_SPLIT_FILES, ARG_SPLIT_ALL, ARG_SPLIT_DIRECTORY, ARG_SPLIT_OUTPUT, ARG_SPLIT_MAPPING, ARG_SPLIT_INDEX_ON_DEVICE, ARG_MERGE_WINDOW_BYTES };
   static struct option long_options[] = {{"tmp-directory", 1, 0, 'T'}, {"rank", 1, 0, 'r'}, {"version", 0, 0, ARG_VERSION}, {"import-on-device", 0, 0, ARG_IMPORT_ON_DEVICE},
-                                         {"inflate-on-host", 0, 0, ARG_INFLATE_ON_HOST},
+                                         {"inflate-on-host", 0, 0, ARG_INFLATE_ON_HOST}, {"merge-window-bytes", 1, 0, ARG_MERGE_WINDOW_BYTES},
                                          {"split-files", 0, 0, ARG_SPLIT_FILES}, {"split-all-partitions", 0, 0, ARG_SPLIT_ALL},
                                          {"split-files-results-directory", 1, 0, ARG_SPLIT_DIRECTORY}, {"split-output-filename", 1, 0, ARG_SPLIT_OUTPUT},
                                          {"split-callset-mapping-file", 0, 0, ARG_SPLIT_MAPPING}, {"split-index-on-device", 0, 0, ARG_SPLIT_INDEX_ON_DEVICE},
@@ -134,6 +137,8 @@ int main(int argc, char** argv) {
   int rank = launcher_rank();
   bool import_on_device = false, inflate_on_host = false;
   bool split_index_on_device = false;
+  bool merge_windowed = false;
+  uint64_t merge_window_bytes = 0;
   bool split_files = false, split_all = false, split_mapping = false;      // (any of the five split options turns splitting on; the reference needs --split-files next to the others)
   std::string split_directory, split_output;
   int c;
@@ -144,6 +149,7 @@ int main(int argc, char** argv) {
       case ARG_VERSION: std::cout << "genomicsdb_amd (MI355X variant-combine path) for GenomicsDB 0.10.2 loader JSON\n"; return 0;
       case ARG_IMPORT_ON_DEVICE: import_on_device = true; break;
       case ARG_INFLATE_ON_HOST: inflate_on_host = true; break;
+      case ARG_MERGE_WINDOW_BYTES: merge_windowed = true; merge_window_bytes = strtoull(optarg, nullptr, 10); break;
       case ARG_SPLIT_FILES: split_files = true; break;
       case ARG_SPLIT_ALL: split_files = true; split_all = true; break;
       case ARG_SPLIT_DIRECTORY: split_files = true; split_directory = optarg; break;
@@ -193,6 +199,7 @@ int main(int argc, char** argv) {
                 << ",host_inflated_files," << st.num_host_inflated_files << ",inflate_kernel_ms," << st.ms_inflate << "\n";
     LoaderOutputs out;
     out.loader_text = loader_text; out.rank = rank; out.device = device; out.tool = "vcf2tiledb";
+    out.merge_windowed = merge_windowed; out.merge_window_bytes = merge_window_bytes;
     produce_loader_outputs(out, doc, loader, &cells);
   } catch (const std::exception& e) {
     std::cerr << "vcf2tiledb: " << e.what() << "\n";

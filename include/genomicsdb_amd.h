@@ -364,6 +364,19 @@ int gdbamd_import_cells_device_rows(const char* vid_mapping_file, const char* ca
 #define GDBAMD_MERGE_NUM_STATS 12
 int gdbamd_merge_cells(int nstreams, const void* const* data, const uint64_t* nbytes, uint8_t** cells, uint64_t* out_nbytes, int64_t* ncells, int device,
                        double* stats, int nstats);
+/* The same merge from files to a file, for arrays larger than device memory: source i is the file paths[i], read with pread, or, when paths[i] is NULL, the
+ * nbytes[i] bytes at data[i] (paths or data may be NULL as a whole when no source is of that kind).  The sources are merged round by round through pinned
+ * staging and device pools bounded by window_bytes - the input cell bytes resident on the device, carried and fresh, over all sources; 0: derived from the
+ * free device memory - with the transfers overlapped with the kernels; a round that can emit nothing (a cell, or a run of one key, larger than a source's
+ * share of the window) doubles that share.  The result, byte for byte what gdbamd_merge_cells gives, goes to <output_path>.merge.tmp and is renamed to
+ * output_path on success; after an error neither is left.  The refusals are those of gdbamd_merge_cells with cell indices and byte offsets counted from the
+ * start of the source; the shared row named is the smallest one known in the round that first finds one.  Device memory: about 8.7 x window_bytes plus
+ * nsources x largest row / 8 bytes, whatever the sources' lengths.  Returns the number of cells, -1: error.  stats: NULL or nstats doubles:
+ *   0..11 as gdbamd_merge_cells (HIP-event ms summed over the rounds; 9, 10 stay 0), 12 rounds, 13 cells carried (summed over the rounds), 14 growths of a
+ *   share, 15 window bytes as used, 16 peak device bytes, 17 pinned host bytes, 18..20 wall seconds of the host thread reading, writing, waiting for the device */
+#define GDBAMD_MERGE_FILES_NUM_STATS 21
+int64_t gdbamd_merge_cell_files(int nsources, const char* const* paths, const void* const* data, const uint64_t* nbytes, const char* output_path, int device,
+                                uint64_t window_bytes, double* stats, int nstats);
 /* vcf2tiledb --split-files on GPU `device` (kernels/gdb_split.hip; reference tools/src/vcf2tiledb.cc:118-151): every (g)VCF text file of the callset
  * mapping - plain, gzip or BGZF; then the nextra paths of extra_paths - is cut into one BGZF file + <file>.tbi per column partition, in one pass per file.
  * Partition p is [begins[p], ends[p]] (the loader JSON's column_partitions with derived ends; they must not overlap, at most 4096).  A partition's file holds
