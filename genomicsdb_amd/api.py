@@ -800,4 +800,29 @@ def bgzf_decompress(data, device=0):
     return dst.raw[:n.value], ms.value
 
 
+TILE_BYTES = 8192
+
+
+def inflate_tiles(streams, wants, device=0, fill=0xA5):
+    """N independent raw DEFLATE streams through the tile inflater of compressed fragment files (k_inflate_tiles, with the launch
+    shape and buffer sizes of the fragment reader): stream i must inflate to exactly wants[i] <= 8192 bytes.  The streams are
+    concatenated without padding.  Returns (status, out): status[i] = 0 or the TileErr of csrc/core/gdb_tile_inflate.hpp, out =
+    N slots of 8192 bytes, each prefilled with `fill` before the launch.  A diagnostic: the engine path does not use it."""
+    L = _lib.lib()
+    streams = [bytes(s) for s in streams]
+    n = len(streams)
+    if len(wants) != n:
+        raise ValueError("inflate_tiles: one size per stream")
+    if n == 0:
+        return b"", b""
+    offs = (ctypes.c_uint64 * (n + 1))()
+    for i, s in enumerate(streams):
+        offs[i + 1] = offs[i] + len(s)
+    want = (ctypes.c_uint32 * n)(*[int(w) for w in wants])
+    out = ctypes.create_string_buffer(n * TILE_BYTES)
+    status = ctypes.create_string_buffer(n)
+    _check(L.gdbamd_inflate_tiles(b"".join(streams), offs, want, n, int(fill) & 0xFF, out, status, int(device)) == 0, "inflate_tiles")
+    return status.raw[:n], out.raw[:n * TILE_BYTES]
+
+
 BGZF_EOF = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0])

@@ -228,6 +228,14 @@ def build_hostsim_inflate():
     return os.path.join(ROOT, "tests", "hostsim_inflate", "libhostsim_inflate.so")
 
 
+def build_hostsim_tile_inflate():
+    """CPU harness around the body of the tile inflater of compressed fragment files (core/gdb_tile_inflate.hpp) and a stand-alone
+    driver of the same body built with the address and undefined-behaviour sanitizers (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_tile_inflate")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_tile_inflate.so"), os.path.join(d, "tile_inflate_fuzz")
+
+
 def build_hostsim_dispatch():
     """CPU harness around the choice of an interval's sizing and page kernels (kernels/gdb_assembly_choice.hpp; tests only)"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_dispatch")])

@@ -187,6 +187,15 @@ int gdbamd_bgzf_decompress(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_
     return 0;
   }, -1);
 }
+// independent DEFLATE tiles through the tile inflater of the fragment reader (k_inflate_tiles; a diagnostic and its test hook)
+int gdbamd_inflate_tiles(const uint8_t* src, const uint64_t* in_off, const uint32_t* want, uint64_t ntiles, uint8_t fill, uint8_t* out, uint8_t* status, int device) {
+  return guarded([&]() -> int {
+    if (!in_off || (ntiles && (!want || !out || !status)) || (ntiles && in_off[ntiles] && !src)) throw GenomicsDBConfigException("gdbamd_inflate_tiles: null argument");
+    if (DevicePipeline::device_count() <= 0) throw GenomicsDBDeviceException("no HIP device visible");
+    inflate_tiles_on_device(src, in_off, want, ntiles, fill, out, status, device);
+    return 0;
+  }, -1);
+}
 void gdbamd_engine_destroy(void* e) { delete (EngineHandle*)e; }
 int gdbamd_engine_num_fields(void* e) { return e ? ((EngineHandle*)e)->eng->plan().plan.nfields : -1; }
 const char* gdbamd_engine_field_name(void* e, int f) {

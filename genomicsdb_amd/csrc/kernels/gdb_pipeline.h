@@ -174,4 +174,9 @@ class DevicePipeline {
   Impl* m_;
 };
 
+// diagnostic: ntiles independent DEFLATE tiles (stream t = comp[in_off[t], in_off[t + 1]), to inflate to want[t] <= 8192 bytes) through the
+// tile inflater of the fragment reader, same kernel, launch shape and buffer sizes; out: ntiles * 8192 bytes prefilled with `fill`,
+// status: the gdbtile::TileErr of every tile (core/gdb_tile_inflate.hpp)
+void inflate_tiles_on_device(const uint8_t* comp, const uint64_t* in_off, const uint32_t* want, uint64_t ntiles, uint8_t fill, uint8_t* out, uint8_t* status, int device);
+
 }  // namespace genomicsdb_amd

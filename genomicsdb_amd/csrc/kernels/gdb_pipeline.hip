@@ -29,6 +29,7 @@
 #include "../core/gdb_bcf.hpp"
 #include "../core/gdb_calls.hpp"
 #include "../core/gdb_variants.hpp"
+#include "../core/gdb_tile_inflate.hpp"
 #include "gdb_pipeline.h"
 #include "gdb_bgzf.h"
 #include "gdb_assembly_choice.hpp"
@@ -3810,7 +3811,7 @@ struct DevicePipeline::Impl {
   // the walk of the cell sizes on the device
   DevBuf<uint64_t> walk_bitmap, walk_pos, walk_out; DevBuf<uint32_t> walk_wcount, walk_wrank, walk_succ, walk_jump_a, walk_jump_b, walk_flag, walk_dest; DevBuf<uint8_t> walk_reach;
   DevBuf<int64_t> walk_cut; DevBuf<unsigned long long> walk_kept_bytes;
-  DevBuf<uint8_t> inflate_in, inflate_out, inflate_scratch; DevBuf<uint64_t> inflate_off; DevBuf<uint32_t> inflate_want;   // DEFLATE tiles of a compressed fragment file
+  DevBuf<uint8_t> inflate_in, inflate_out, inflate_scratch, inflate_status; DevBuf<uint64_t> inflate_off; DevBuf<uint32_t> inflate_want;   // DEFLATE tiles of a compressed fragment file
   DevBuf<long long> carry_last; DevBuf<uint64_t> carry_keys, carry_sorted; int64_t carried_cells = 0;
   DevBuf<uint2> chk_resolved; DevBuf<uint64_t> chk_sizes; DevBuf<unsigned long long> chk_count;   // GDBAMD_SIZE3_CHECK
   DevBuf<uint2> resolved;          // (pool offset, length) of every (record, sample): whole interval, or one page when that exceeds the budget
@@ -4403,188 +4404,17 @@ namespace {
 // DEFLATE stream (RFC 1951) of its own - the analogue of the gzip'd attribute tiles of the reference's TileDB arrays
 // (genomicsdb_iterators.cc:334-423 reads them tile by tile).  Compressed bytes cross PCIe, one thread inflates one tile:
 // a window has tens of thousands of tiles, so the serial bit-by-bit nature of a DEFLATE stream is spread over as many lanes.
-// The writer (save_fragment, zlib with strategy Z_FIXED) emits stored and FIXED-Huffman blocks only: the decoder then needs no
-// per-stream code tables - a literal / length code is 7 to 9 bits and is classified arithmetically (RFC 1951, 3.2.6).  Blocks with
-// dynamic codes (a file compressed by something else) are decoded too, with tables in memory; a malformed or overlong stream raises
-// an error bit.
-constexpr uint32_t kFragTile = 8192;
-__device__ const uint16_t kInfLenBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-__device__ const uint8_t kInfLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-__device__ const uint16_t kInfDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-__device__ const uint8_t kInfDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-struct InflateBits {
-  const uint8_t* p; const uint8_t* end;
-  uint64_t buf; int n;
-  // After refill() at least 33 bits are buffered while input remains (no consumer takes more than 19 between two refills).  Eight
-  // bytes at a time while they last: the stream is read front to back by one lane, one unaligned 8-byte load per 3 to 7 bytes used.
-  __device__ __forceinline__ void refill() {
-    if (n > 32) return;
-    if (p + 8 <= end) {
-      uint64_t w;
-      __builtin_memcpy(&w, p, 8);
-      buf |= w << n;
-      const int take = (63 - n) >> 3;
-      p += take; n += take * 8;
-      buf &= (1ull << n) - 1ull;                 // (n <= 63: the bits of the byte that was not taken are read again next time)
-    } else while (n <= 56 && p < end) { buf |= (uint64_t)(*p++) << n; n += 8; }
-  }
-  __device__ __forceinline__ uint32_t peek(int k) const { return (uint32_t)(buf & ((1ull << k) - 1ull)); }
-  __device__ __forceinline__ void drop(int k) { buf >>= k; n -= k; }
-  __device__ __forceinline__ uint32_t get(int k) { const uint32_t v = peek(k); drop(k); return v; }   // (k <= 16; refill() first)
-};
-// Blocks with DYNAMIC codes (what a default zlib / gzip writer produces): canonical Huffman decoding bit by bit over a count-per-length
-// and a symbols-in-code-order table (RFC 1951, 3.2.2 and 3.2.7), the tables of a lane in its own slice of a global scratch buffer.
-// Slower than the fixed codes (up to 15 steps per symbol, tables in memory) - the files this build writes do not need it.
-struct InflateCode { uint16_t* count; uint16_t* symbol; };            // count[16], symbol[n]
-constexpr int kInflateScratch = 320 + 2 * (16 + 288) + 2 * (16 + 32);  // bytes per lane: code lengths, literal / length code, distance code
-__device__ __forceinline__ int inflate_decode(InflateBits& b, const InflateCode& h) {
-  int code = 0, first = 0, index = 0;
-  b.refill();
-  for (int len = 1; len <= 15; ++len) {
-    if (b.n < 1) return -1;
-    code |= (int)b.get(1);
-    const int count = h.count[len];
-    if (code - count < first) return h.symbol[index + (code - first)];
-    index += count; first += count;
-    first <<= 1; code <<= 1;
-    if (len == 8) b.refill();
-  }
-  return -1;
-}
-// code lengths -> tables; returns the number of unused codes (0: complete; < 0: over-subscribed)
-__device__ __forceinline__ int inflate_construct(const InflateCode& h, const uint8_t* length, int n) {
-  for (int len = 0; len <= 15; ++len) h.count[len] = 0;
-  for (int sym = 0; sym < n; ++sym) h.count[length[sym]]++;
-  if (h.count[0] == n) return 0;
-  int left = 1;
-  for (int len = 1; len <= 15; ++len) { left <<= 1; left -= h.count[len]; if (left < 0) return left; }
-  uint16_t offs[16];
-  offs[1] = 0;
-  for (int len = 1; len < 15; ++len) offs[len + 1] = (uint16_t)(offs[len] + h.count[len]);
-  for (int sym = 0; sym < n; ++sym) if (length[sym] != 0) h.symbol[offs[length[sym]]++] = (uint16_t)sym;
-  return left;
-}
-// The copy of a match: 8 bytes per load / store while the distance allows it (a copy with dist >= 8 never reads a byte its own
-// current 8-byte store writes; bytes written by EARLIER stores of the same lane are seen - the vector memory pipeline keeps one
-// lane's accesses to an address in order, which the byte-by-byte loop of round 2 relied on as well).  The byte loop made every
-// copied byte a global load behind a global store - one memory round trip per byte, the largest item of the kernel's time.
-__device__ __forceinline__ void inflate_copy_match(uint8_t* o, uint32_t at, uint32_t len, uint32_t dist) {
-  uint32_t i = 0;
-  if (dist >= 8u)
-    for (; i + 8u <= len; i += 8u) { uint64_t w; __builtin_memcpy(&w, o + at - dist + i, 8); __builtin_memcpy(o + at + i, &w, 8); }
-  for (; i < len; ++i) o[at + i] = o[at + i - dist];
-}
-// job t: compressed bytes [in_off[t], in_off[t + 1]) of `comp` -> want[t] bytes at out + t * kFragTile
+// The decoder itself is core/gdb_tile_inflate.hpp (gdbtile::tile_inflate), which the CPU harness tests/hostsim_tile_inflate runs too.
+constexpr uint32_t kFragTile = gdbtile::kTileBytes;
+constexpr int kInflateScratch = gdbtile::kTileScratch;
+// job t: compressed bytes [in_off[t], in_off[t + 1]) of `comp` -> want[t] bytes at out + t * kFragTile; tile_status (may be null): the TileErr of every job
 __global__ void k_inflate_tiles(const uint8_t* __restrict__ comp, const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ want_bytes, int64_t ntiles, uint8_t* __restrict__ out,
-                                uint8_t* __restrict__ scratch, uint32_t* err) {
+                                uint8_t* __restrict__ scratch, uint32_t* err, uint8_t* __restrict__ tile_status) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntiles) return;
-  uint8_t* const lengths = scratch + (uint64_t)t * kInflateScratch;                                       // [320]
-  const InflateCode lencode{reinterpret_cast<uint16_t*>(lengths + 320), reinterpret_cast<uint16_t*>(lengths + 320) + 16};
-  const InflateCode distcode{lencode.symbol + 288, lencode.symbol + 288 + 16};
-  uint8_t* const o = out + (uint64_t)t * kFragTile;
-  const uint32_t want = want_bytes[t];
-  InflateBits b{comp + in_off[t], comp + in_off[t + 1], 0ull, 0};
-  uint32_t at = 0;
-  bool bad = false, last = false;
-  while (!last && !bad) {
-    b.refill();
-    if (b.n < 3) { bad = true; break; }
-    last = b.get(1) != 0;
-    const uint32_t type = b.get(2);
-    if (type == 0) {                                   // stored: LEN, NLEN, bytes
-      b.drop(b.n & 7);
-      b.refill();
-      if (b.n < 32) { bad = true; break; }
-      const uint32_t len = b.get(16), nlen = b.get(16);
-      if ((len ^ nlen) != 0xFFFFu || at + len > want) { bad = true; break; }
-      for (uint32_t i = 0; i < len; ++i) { b.refill(); if (b.n < 8) { bad = true; break; } o[at++] = (uint8_t)b.get(8); }
-    } else if (type == 1) {                            // fixed Huffman codes
-      for (;;) {
-        b.refill();
-        if (b.n < 7) { bad = true; break; }
-        uint32_t sym;
-        const uint32_t c7 = __brev(b.peek(7)) >> 25;   // Huffman codes are packed most-significant bit first
-        if (c7 <= 0x17u) { sym = 256u + c7; b.drop(7); }
-        else {
-          const uint32_t c8 = __brev(b.peek(8)) >> 24;
-          if (c8 >= 0x30u && c8 <= 0xBFu) { sym = c8 - 0x30u; b.drop(8); }
-          else if (c8 >= 0xC0u && c8 <= 0xC7u) { sym = 280u + (c8 - 0xC0u); b.drop(8); }
-          else {
-            const uint32_t c9 = __brev(b.peek(9)) >> 23;
-            if (c9 < 0x190u) { bad = true; break; }
-            sym = 144u + (c9 - 0x190u); b.drop(9);
-          }
-        }
-        if (b.n < 0) { bad = true; break; }
-        if (sym < 256u) { if (at >= want) { bad = true; break; } o[at++] = (uint8_t)sym; continue; }
-        if (sym == 256u) break;
-        if (sym > 285u) { bad = true; break; }
-        b.refill();
-        const uint32_t li = sym - 257u;
-        const uint32_t len = kInfLenBase[li] + b.get(kInfLenExtra[li]);
-        const uint32_t dc = __brev(b.get(5)) >> 27;
-        if (dc >= 30u) { bad = true; break; }
-        b.refill();
-        const uint32_t dist = kInfDistBase[dc] + b.get(kInfDistExtra[dc]);
-        if (b.n < 0 || dist > at || at + len > want) { bad = true; break; }
-        inflate_copy_match(o, at, len, dist);
-        at += len;
-      }
-    } else if (type == 2) {                            // dynamic codes: read the code lengths, build both tables, decode
-      b.refill();
-      if (b.n < 14) { bad = true; break; }
-      const int nlen = (int)b.get(5) + 257, ndist = (int)b.get(5) + 1, ncode = (int)b.get(4) + 4;
-      if (nlen > 286 || ndist > 30) { bad = true; break; }
-      const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-      for (int i = 0; i < 19; ++i) lengths[i] = 0;
-      for (int i = 0; i < ncode; ++i) { b.refill(); if (b.n < 3) { bad = true; break; } lengths[order[i]] = (uint8_t)b.get(3); }
-      if (bad) break;
-      if (inflate_construct(lencode, lengths, 19) != 0) { bad = true; break; }       // the code-length code must be complete
-      int index = 0;
-      while (index < nlen + ndist && !bad) {
-        int sym = inflate_decode(b, lencode);
-        if (sym < 0) { bad = true; break; }
-        if (sym < 16) lengths[index++] = (uint8_t)sym;
-        else {
-          int rep_len = 0;
-          b.refill();
-          if (sym == 16) { if (index == 0) { bad = true; break; } rep_len = lengths[index - 1]; sym = 3 + (int)b.get(2); }
-          else if (sym == 17) sym = 3 + (int)b.get(3);
-          else sym = 11 + (int)b.get(7);
-          if (b.n < 0 || index + sym > nlen + ndist) { bad = true; break; }
-          while (sym--) lengths[index++] = (uint8_t)rep_len;
-        }
-      }
-      if (bad) break;
-      if (lengths[256] == 0) { bad = true; break; }                                 // no end-of-block code
-      // (the distance lengths are moved aside first: building the literal / length tables must not clobber them)
-      uint8_t dlen[30];
-      for (int i = 0; i < ndist; ++i) dlen[i] = lengths[nlen + i];
-      int rc = inflate_construct(lencode, lengths, nlen);
-      if (rc < 0 || (rc > 0 && nlen - lencode.count[0] != 1)) { bad = true; break; }
-      rc = inflate_construct(distcode, dlen, ndist);
-      if (rc < 0 || (rc > 0 && ndist - distcode.count[0] != 1)) { bad = true; break; }
-      for (;;) {
-        const int sym = inflate_decode(b, lencode);
-        if (sym < 0) { bad = true; break; }
-        if (sym < 256) { if (at >= want) { bad = true; break; } o[at++] = (uint8_t)sym; continue; }
-        if (sym == 256) break;
-        if (sym > 285) { bad = true; break; }
-        b.refill();
-        const uint32_t li = (uint32_t)sym - 257u;
-        const uint32_t len = kInfLenBase[li] + b.get(kInfLenExtra[li]);
-        const int dc = inflate_decode(b, distcode);
-        if (dc < 0 || dc >= 30) { bad = true; break; }
-        b.refill();
-        const uint32_t dist = kInfDistBase[dc] + b.get(kInfDistExtra[dc]);
-        if (b.n < 0 || dist > at || at + len > want) { bad = true; break; }
-        inflate_copy_match(o, at, len, dist);
-        at += len;
-      }
-    } else bad = true;                                 // the reserved block type
-  }
-  if (bad || at != want) atomicOr(err, (uint32_t)GDB_ERR_CELL_STREAM);
+  const gdbtile::TileErr e = gdbtile::tile_inflate(comp + in_off[t], comp + in_off[t + 1], want_bytes[t], out + (uint64_t)t * kFragTile, scratch + (uint64_t)t * kInflateScratch);
+  if (e != gdbtile::TILE_OK) atomicOr(err, (uint32_t)GDB_ERR_CELL_STREAM);
+  if (tile_status) tile_status[t] = (uint8_t)e;
 }
 
 const char kFragMagic[8] = {'G', 'D', 'B', 'A', 'M', 'D', 'F', '2'};
@@ -4947,7 +4777,9 @@ DevicePipeline::FragmentWindow DevicePipeline::append_fragment_cells(int64_t c0,
   std::vector<uint32_t> job_want;
   std::vector<InflateCopy> copies;
   std::vector<std::pair<uint64_t, uint64_t>> file_ranges;      // (file offset, bytes) of the compressed bytes, in job order
-  auto section_to_device = [&](const FragmentFile::Section& sec, void* dev, uint64_t a, uint64_t nbytes) {
+  struct JobSection { uint64_t first_job, first_tile; std::string what; };   // the jobs from first_job on are the tiles from first_tile on of section `what`
+  std::vector<JobSection> job_sections;
+  auto section_to_device = [&](const FragmentFile::Section& sec, void* dev, uint64_t a, uint64_t nbytes, const std::string& what) {
     if (a + nbytes > sec.bytes) throw std::runtime_error(F.path + ": read beyond a section of the fragment file");
     if (!sec.compressed) { F.to_device(dev, sec.at + a, nbytes, st); return; }
     if (nbytes == 0) return;
@@ -4961,26 +4793,37 @@ DevicePipeline::FragmentWindow DevicePipeline::append_fragment_cells(int64_t c0,
       job_want.push_back((uint32_t)std::min<uint64_t>(kFragTile, sec.bytes - (t0 + i) * kFragTile));
     }
     file_ranges.emplace_back(sec.at + offs[0], offs[nt] - offs[0]);
+    job_sections.push_back(JobSection{first_job, t0, what});
     copies.push_back(InflateCopy{dev, first_job * kFragTile + (a - t0 * kFragTile), nbytes});
   };
-  section_to_device(F.sec_row, row, (uint64_t)c0 * 4, (uint64_t)n * 4);
-  section_to_device(F.sec_begin, begin, (uint64_t)c0 * 8, (uint64_t)n * 8);
-  section_to_device(F.sec_end, end, (uint64_t)c0 * 8, (uint64_t)n * 8);
+  section_to_device(F.sec_row, row, (uint64_t)c0 * 4, (uint64_t)n * 4, "row");
+  section_to_device(F.sec_begin, begin, (uint64_t)c0 * 8, (uint64_t)n * 8, "begin");
+  section_to_device(F.sec_end, end, (uint64_t)c0 * 8, (uint64_t)n * 8, "end");
   auto inflate_all = [&]() {
     const uint64_t njobs = job_want.size();
     if (njobs == 0) return;
     S.inflate_in.ensure(job_in.back() + 16); S.inflate_off.ensure((size_t)njobs + 1); S.inflate_want.ensure((size_t)njobs); S.inflate_out.ensure(njobs * kFragTile);
-    S.inflate_scratch.ensure(njobs * (size_t)kInflateScratch);
+    S.inflate_scratch.ensure(njobs * (size_t)kInflateScratch); S.inflate_status.ensure((size_t)njobs);
     uint64_t at_in = 0;
     for (auto& fr : file_ranges) { F.to_device(S.inflate_in.p + at_in, fr.first, fr.second, st); at_in += fr.second; }
     HIP_CHECK(hipMemcpyAsync(S.inflate_off.p, job_in.data(), (size_t)(njobs + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(S.inflate_want.p, job_want.data(), (size_t)njobs * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_inflate_tiles, dim3(blocks_for((int64_t)njobs, 64)), dim3(64), 0, st, (const uint8_t*)S.inflate_in.p, (const uint64_t*)S.inflate_off.p, (const uint32_t*)S.inflate_want.p,
-                       (int64_t)njobs, S.inflate_out.p, S.inflate_scratch.p, S.err.p);
+                       (int64_t)njobs, S.inflate_out.p, S.inflate_scratch.p, S.err.p, S.inflate_status.p);
     for (auto& c : copies) HIP_CHECK(hipMemcpyAsync(c.dev, S.inflate_out.p + c.from, c.bytes, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));                          // (the host vectors above are read by the copies)
     if (S.read_back(S.err.p) != 0u) {
-      throw std::runtime_error(F.path + ": a compressed tile does not inflate to its size (corrupt file)");
+      // (the status of every tile is read back only now: the first one that failed names its section, its tile and the reason)
+      std::vector<uint8_t> status((size_t)njobs);
+      HIP_CHECK(hipMemcpy(status.data(), S.inflate_status.p, (size_t)njobs, hipMemcpyDeviceToHost));
+      std::string where;
+      for (uint64_t j = 0; j < njobs && where.empty(); ++j) {
+        if (status[(size_t)j] == gdbtile::TILE_OK) continue;
+        size_t k = 0;
+        while (k + 1 < job_sections.size() && job_sections[k + 1].first_job <= j) ++k;
+        where = ": section " + job_sections[k].what + ", tile " + std::to_string(job_sections[k].first_tile + (j - job_sections[k].first_job)) + ": " + gdbtile::tile_err_text(status[(size_t)j]);
+      }
+      throw std::runtime_error(F.path + ": a compressed tile does not inflate to its size (corrupt file)" + where);
     }
   };
   auto rebase_offsets = [&]() {
@@ -4999,17 +4842,17 @@ DevicePipeline::FragmentWindow DevicePipeline::append_fragment_cells(int64_t c0,
       F.host_read(fd.off, (uint64_t)c0 * 4, &o0, 4); F.host_read(fd.off, (uint64_t)c1 * 4, &o1, 4);
       if (o1 < o0 || (uint64_t)o1 * (uint64_t)fd.elem_size > fd.data_bytes) throw std::runtime_error(F.path + ": corrupt offsets in a variable-length column");
       uint32_t* off = (uint32_t*)alloc(((size_t)n + 1) * 4);
-      section_to_device(fd.off, off, (uint64_t)c0 * 4, ((uint64_t)n + 1) * 4);
+      section_to_device(fd.off, off, (uint64_t)c0 * 4, ((uint64_t)n + 1) * 4, S.hp.field_names[(size_t)f] + " offsets");
       rebase.push_back(Rebase{off, (uint32_t)(0u - o0), o1 - o0});   // (rebased to the part once the tiles are inflated)
       const uint64_t bytes = (uint64_t)(o1 - o0) * (uint64_t)fd.elem_size;
       void* data = alloc((size_t)bytes);
-      section_to_device(fd.data, data, (uint64_t)o0 * (uint64_t)fd.elem_size, bytes);
+      section_to_device(fd.data, data, (uint64_t)o0 * (uint64_t)fd.elem_size, bytes, S.hp.field_names[(size_t)f] + " data");
       part.v.col[f].off = off; part.v.col[f].data = data;
       part.data_bytes[(size_t)f] = (size_t)bytes;
     } else {
       const uint64_t bpc = (uint64_t)fd.fixed_num * (uint64_t)fd.elem_size;
       void* data = alloc((size_t)((uint64_t)n * bpc));
-      section_to_device(fd.data, data, (uint64_t)c0 * bpc, (uint64_t)n * bpc);
+      section_to_device(fd.data, data, (uint64_t)c0 * bpc, (uint64_t)n * bpc, S.hp.field_names[(size_t)f] + " data");
       part.v.col[f].data = data;
       part.data_bytes[(size_t)f] = (size_t)((uint64_t)n * bpc);
     }
@@ -5038,6 +4881,39 @@ DevicePipeline::FragmentWindow DevicePipeline::append_fragment_cells(int64_t c0,
   S.parts.push_back(part);
   guard.keep = true;
   return w;
+}
+
+// Diagnostic entry (gdbamd_inflate_tiles): ntiles independent DEFLATE streams, concatenated without padding, through k_inflate_tiles
+// with the launch shape and the buffer sizes of append_fragment_cells above.  Every output slot of kFragTile bytes is prefilled
+// with `fill`; out: ntiles * kFragTile bytes, status: the TileErr of every tile.  Not part of the engine path.
+void inflate_tiles_on_device(const uint8_t* comp, const uint64_t* in_off, const uint32_t* want, uint64_t ntiles, uint8_t fill, uint8_t* out, uint8_t* status, int device) {
+  if (ntiles == 0) return;
+  if (in_off[0] != 0) throw GenomicsDBDeviceException("inflate_tiles: the first offset is not 0");
+  for (uint64_t t = 0; t < ntiles; ++t) {
+    if (in_off[t + 1] < in_off[t]) throw GenomicsDBDeviceException("inflate_tiles: offsets decrease");
+    if (want[t] > kFragTile) throw GenomicsDBDeviceException("inflate_tiles: a tile has at most " + std::to_string(kFragTile) + " bytes");
+  }
+  HIP_CHECK(hipSetDevice(device));
+  DevBuf<uint8_t> d_in, d_out, d_scratch, d_status; DevBuf<uint64_t> d_off; DevBuf<uint32_t> d_want, d_err;
+  d_in.ensure((size_t)in_off[ntiles] + 16); d_off.ensure((size_t)ntiles + 1); d_want.ensure((size_t)ntiles); d_out.ensure((size_t)ntiles * kFragTile);
+  d_scratch.ensure((size_t)ntiles * (size_t)kInflateScratch); d_status.ensure((size_t)ntiles); d_err.ensure(1);
+  if (in_off[ntiles]) HIP_CHECK(hipMemcpy(d_in.p, comp, (size_t)in_off[ntiles], hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_off.p, in_off, (size_t)(ntiles + 1) * 8, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_want.p, want, (size_t)ntiles * 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_out.p, fill, (size_t)ntiles * kFragTile));
+  HIP_CHECK(hipMemset(d_status.p, 0xFF, (size_t)ntiles));
+  HIP_CHECK(hipMemset(d_err.p, 0, sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_inflate_tiles, dim3(blocks_for((int64_t)ntiles, 64)), dim3(64), 0, 0, (const uint8_t*)d_in.p, (const uint64_t*)d_off.p, (const uint32_t*)d_want.p, (int64_t)ntiles, d_out.p,
+                     d_scratch.p, d_err.p, d_status.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(out, d_out.p, (size_t)ntiles * kFragTile, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(status, d_status.p, (size_t)ntiles, hipMemcpyDeviceToHost));
+  uint32_t err = 0;
+  HIP_CHECK(hipMemcpy(&err, d_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  bool any = false;
+  for (uint64_t t = 0; t < ntiles; ++t) any = any || status[t] != 0;
+  if (any != ((err & (uint32_t)GDB_ERR_CELL_STREAM) != 0u)) throw GenomicsDBDeviceException("inflate_tiles: the error bit and the tile status disagree");
 }
 
 FragmentFileMeta DevicePipeline::load_fragment(const std::string& path, const std::vector<ColumnLayout>& expected, uint64_t expected_schema_hash) {

@@ -190,8 +190,16 @@ int64_t gdbamd_equi_partition_text(const uint64_t* counts, uint64_t nbins, uint6
 int gdbamd_engine_save_fragment(void* engine, const char* path);
 /* the same file with every data section cut into 8 KiB tiles, each a raw DEFLATE stream (stored / fixed-Huffman blocks): compressed
  * bytes cross PCIe and are inflated on the device (fixed and dynamic Huffman codes), one thread per tile (the place of the gzip'd attribute tiles of the reference's
- * TileDB arrays, genomicsdb_iterators.cc:334-423) */
+ * TileDB arrays, genomicsdb_iterators.cc:334-423).  Tiles carry no checksum: a tile whose stream is malformed or does not inflate to the
+ * tile's size is refused at load (the error names the section, the tile and the reason); damage that leaves a valid stream of the
+ * same size is NOT detected ("Compressed fragment files"). */
 int gdbamd_engine_save_fragment_compressed(void* engine, const char* path);
+/* diagnostic and test hook of that tile inflater: ntiles independent raw DEFLATE streams, concatenated without padding (stream t =
+ * bytes [in_off[t], in_off[t + 1]) of src, in_off[0] = 0), through the kernel and launch shape the fragment reader uses on GPU `device`.
+ * want[t] <= 8192 = the size tile t must inflate to.  out: ntiles * 8192 bytes, every slot prefilled with `fill` before the launch;
+ * status[t]: 0 = inflated to exactly want[t] bytes, else why not (1 block type, 2 code, 3 no end-of-block, 4 symbol, 5 distance,
+ * 6 more output than want, 7 input exhausted, 8 LEN / NLEN, 9 fewer bytes than want).  0 on success (refused tiles are no error). */
+int gdbamd_inflate_tiles(const uint8_t* src, const uint64_t* in_off, const uint32_t* want, uint64_t ntiles, uint8_t fill, uint8_t* out, uint8_t* status, int device);
 int gdbamd_engine_load_fragment(void* engine, const char* path);
 /* Arrays larger than the staging budget (GDBAMD_STAGE_BUDGET_MB, default 8192 MiB of cells per window): instead of staging by
  * hand, name a source and let the engine pass it through HBM in column windows, carrying the intervals that are still live at a

@@ -1576,6 +1576,7 @@ def test_compressed_fragment_file_is_inflated_on_the_device(gdb, tmp_path, monke
     import json
     import os
     import struct
+    import sys
     import zlib
     from genomicsdb_amd import synth
     N, B, L = 150, 10_000_000, 24_000
@@ -1618,76 +1619,28 @@ def test_compressed_fragment_file_is_inflated_on_the_device(gdb, tmp_path, monke
     s.close()
     monkeypatch.delenv("GDBAMD_STAGE_BUDGET_BYTES")
     # (c) the tiles are plain DEFLATE: walk the header to the first data section that has tiles; its first tile inflates with zlib
+    #     (the section walker and the version-3 writer are tests/tools/fragment_file.py)
+    sys.path.insert(0, os.path.join(helpers.ROOT, "tests", "tools"))
+    import fragment_file
     blob = bytearray((ws / "arr" / "fragment.gdbamd").read_bytes())
     assert blob[:8] == b"GDBAMDF2" and struct.unpack_from("<I", blob, 8)[0] == 3
-    nfields, C, M = struct.unpack_from("<Iqq", blob, 12)
-    at = 88
-    fields = []
-    for _ in range(nfields):
-        var, es, name_len, fixed_num, data_bytes = struct.unpack_from("<BBHiQ", blob, at)
-        at += 16 + name_len
-        fields.append((var, data_bytes))
-    nsec = 3 + 2 * nfields                                  # row, begin, end, then (offsets, data) per field
-    stored = struct.unpack_from("<%dQ" % nsec, blob, at)
-    at += 8 * nsec
-    al = lambda x: (x + 63) & ~63
-    # (section size, index into `stored`) in file order; None = the boundary markers, which stay raw
-    layout = [(C * 4, 0), (C * 8, 1), (C * 8, 2), (M * 8, None)]
-    for i, (var, data_bytes) in enumerate(fields):
-        if var:
-            layout.append(((C + 1) * 4, 3 + 2 * i))
-        layout.append((data_bytes, 4 + 2 * i))
+    frag = fragment_file.parse(blob)                        # (asserts the tile count of every section and that the sections end where the file ends)
     payload_at = offs = None
-    for nbytes, si in layout:
-        at = al(at)
-        if si is None:
-            at += nbytes
+    for sec in frag.sections:
+        if sec.tiles is None:
             continue
-        st_bytes = stored[si]
-        ntiles = struct.unpack_from("<Q", blob, at + st_bytes - 8)[0]
-        assert ntiles == (nbytes + 8191) // 8192
-        if ntiles and si >= 3 and payload_at is None:       # the first field section: damaged in (e)
-            index_at = at + st_bytes - 8 - 8 * (ntiles + 1)
-            offs = struct.unpack_from("<%dQ" % (ntiles + 1), blob, index_at)
-            payload_at = at
-            first_len = min(8192, nbytes)
-        at += st_bytes
-    assert at == len(blob) and payload_at is not None
+        assert len(sec.tiles) == (sec.nbytes + 8191) // 8192
+        if sec.tiles and sec.stored_index >= 3 and payload_at is None:       # the first field section: damaged in (e)
+            offs = sec.tile_offs
+            payload_at = sec.at
+            first_len = min(8192, sec.nbytes)
+    assert payload_at is not None
     first = zlib.decompressobj(-15).decompress(bytes(blob[payload_at + offs[0]:payload_at + offs[1]]))
     assert len(first) == first_len
     # (d) the same file with every tile recompressed by a default zlib writer (dynamic Huffman codes, as gzip'd tiles have them): the
     #     device inflate builds the code tables per tile; same bytes out
     def rebuild(blob, recompress):
-        out = bytearray(blob[:88])
-        at = 88
-        for _ in range(nfields):
-            name_len = struct.unpack_from("<H", blob, at + 2)[0]
-            out += blob[at:at + 16 + name_len]
-            at += 16 + name_len
-        stored_pos = len(out)
-        out += b"\x00" * (8 * nsec)
-        at += 8 * nsec
-        pad = lambda buf: buf.extend(b"\x00" * ((64 - len(buf) % 64) % 64))
-        new_stored = list(stored)
-        for nbytes, si in layout:
-            at = al(at); pad(out)
-            if si is None:
-                out += blob[at:at + nbytes]; at += nbytes
-                continue
-            st_bytes = stored[si]
-            nt = (nbytes + 8191) // 8192
-            index_at = at + st_bytes - 8 - 8 * (nt + 1)
-            toffs = struct.unpack_from("<%dQ" % (nt + 1), blob, index_at)
-            tiles = [recompress(zlib.decompressobj(-15).decompress(bytes(blob[at + toffs[i]:at + toffs[i + 1]]))) for i in range(nt)]
-            new_offs = [0]
-            for z in tiles:
-                out += z
-                new_offs.append(new_offs[-1] + len(z))
-            out += struct.pack("<%dQ" % (nt + 1), *new_offs) + struct.pack("<Q", nt)
-            new_stored[si] = new_offs[-1] + 8 * (nt + 1) + 8
-            at += st_bytes
-        struct.pack_into("<%dQ" % nsec, out, stored_pos, *new_stored)
-        return bytes(out)
+        return fragment_file.write_v3(fragment_file.parse(blob), lambda raw, sec, i: recompress(raw))
 
     def dynamic(raw):
         co = zlib.compressobj(9, zlib.DEFLATED, -15)
