@@ -222,6 +222,15 @@ def build_hostsim_columns():
     return os.path.join(d, "libhostsim_columns.so"), os.path.join(d, "hostsim_columns_main")
 
 
+def build_hostsim_numtext():
+    """CPU harness around the number-text bodies, the ALT token iterator (core/gdb_core.hpp) and the first-cell table of the site pass
+    (core/gdb_stages.hpp), and the same source as a stand-alone program built with the address and undefined-behaviour sanitizers
+    (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_numtext")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_numtext.so"), os.path.join(d, "hostsim_numtext_main")
+
+
 def build_hostsim_inflate():
     """CPU harness around the bodies of the BGZF inflater (core/gdb_inflate.hpp; tests only)"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim_inflate")])

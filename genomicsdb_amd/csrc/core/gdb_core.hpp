@@ -201,15 +201,6 @@ GDB_HD bool gdb_next_genotype(int* a, int p, int nalleles) {
   return false;
 }
 
-template <class Sink> GDB_HD void put_u64(Sink& s, uint64_t v) {
-  char buf[20];
-  int n = 0;
-  do { buf[n++] = (char)('0' + (v % 10)); v /= 10; } while (v);
-  while (n) s.put(buf[--n]);
-}
-template <class Sink> GDB_HD void put_i64(Sink& s, int64_t v) {
-  if (v < 0) { s.put('-'); put_u64(s, (uint64_t)(-(v + 1)) + 1u); } else put_u64(s, (uint64_t)v);
-}
 // 32-bit only (no 64-bit division on the hot path): every FORMAT integer goes through here.  The digits are gathered in
 // a register (8 characters in a 64-bit word, first character in the low byte) - no private-memory array.
 GDB_HD uint64_t gdb_pack_digits(uint32_t v, int& n) {   // v < 10^8
@@ -245,6 +236,37 @@ template <class Sink> GDB_HD void put_u32(Sink& s, uint32_t v) {
 template <class Sink> GDB_HD void put_i32(Sink& s, int32_t v) {
   if (v < 0) { s.put('-'); put_u32(s, 0u - (uint32_t)v); } else put_u32(s, (uint32_t)v);
 }
+// exactly eight digits (v < 10^8), zeros in front
+template <class Sink> GDB_HD void put_u32_pad8(Sink& s, uint32_t v) {
+  int n = 0;
+  uint64_t w = gdb_pack_digits(v, n);
+  for (; n < 8; ++n) w = (w << 8) | (uint64_t)'0';
+  put_packed(s, w, 8);
+}
+// 64-bit values (POS, END): below 2^32 the 32-bit path; above, split by 10^8 into 32-bit pieces (at most three: 2^64 < 1.845 x 10^19 < 10^24) -
+// packed digits all the way, no digit buffer and no 64-bit division per digit
+template <class Sink> GDB_HD void put_u64(Sink& s, uint64_t v) {
+  if (v <= 0xFFFFFFFFull) { put_u32(s, (uint32_t)v); return; }
+  const uint64_t hi = v / 100000000ull;                    // < 1.9 x 10^11
+  const uint32_t lo = (uint32_t)(v - hi * 100000000ull);
+  if (hi <= 0xFFFFFFFFull) put_u32(s, (uint32_t)hi);
+  else {
+    const uint64_t top = hi / 100000000ull;                // < 1845
+    put_u32(s, (uint32_t)top);
+    put_u32_pad8(s, (uint32_t)(hi - top * 100000000ull));
+  }
+  put_u32_pad8(s, lo);
+}
+template <class Sink> GDB_HD void put_i64(Sink& s, int64_t v) {
+  if (v < 0) { s.put('-'); put_u64(s, (uint64_t)(-(v + 1)) + 1u); } else put_u64(s, (uint64_t)v);
+}
+// six digits held in a packed word (first digit in the low byte) with a '.' behind the first `ip` of them (ip < 6)
+GDB_HD uint64_t gdb_packed_insert_dot(uint64_t w, int ip) {
+  const uint64_t head = w & ((1ull << (8 * ip)) - 1ull);
+  return head | ((uint64_t)'.' << (8 * ip)) | ((w >> (8 * ip)) << (8 * (ip + 1)));
+}
+// "0." and nz zeros (nz <= 4) as a packed word of 2 + nz characters
+GDB_HD uint64_t gdb_packed_zero_dot() { return 0x303030302E30ull; }
 
 // ---- "%g" of a float, exactly --------------------------------------------------------------------------------------------------
 // htslib's kputd hands every value outside [0.0001, 999999] to printf("%g") (vcf.c / kstring.c; the oracle calls snprintf).  "%g" is
@@ -322,25 +344,21 @@ template <class Sink> GDB_HD void put_float_g(Sink& s, float f) {
   const uint32_t ex = u >> 23, man = u & 0x7FFFFFu;
   uint32_t q; int X;
   gdb_round_6_digits(ex ? man | 0x800000u : man, ex ? (int)ex - 150 : -149, q, X);
-  char dg[6];
-  for (int i = 5; i >= 0; --i) { dg[i] = (char)('0' + q % 10u); q /= 10u; }
+  // the six digits as a packed word (first digit in the low byte); `last` = index of the last digit that is not a trailing zero
   int last = 5;
-  while (last > 0 && dg[last] == '0') --last;
+  { uint32_t t = q; while (last > 0) { const uint32_t t10 = t / 10u; if (t - t10 * 10u) break; t = t10; --last; } }
+  int nd = 0;
+  const uint64_t w = gdb_pack_digits(q, nd);               // q >= 100000: nd = 6
   if (X < -4 || X >= 6) {
-    s.put(dg[0]);
-    if (last > 0) { s.put('.'); for (int i = 1; i <= last; ++i) s.put(dg[i]); }
-    s.put('e');
-    uint32_t ax = (uint32_t)(X < 0 ? -X : X);
-    s.put(X < 0 ? '-' : '+');
-    if (ax < 10u) s.put('0');
-    put_u64(s, ax);
+    if (last > 0) put_packed(s, gdb_packed_insert_dot(w, 1), 2 + last); else s.put((char)(w & 0xFFu));
+    const uint32_t ax = (uint32_t)(X < 0 ? -X : X);       // <= 45: always two digits
+    const uint32_t a10 = ax / 10u;
+    put_packed(s, (uint64_t)'e' | ((uint64_t)(X < 0 ? '-' : '+') << 8) | ((uint64_t)('0' + a10) << 16) | ((uint64_t)('0' + (ax - a10 * 10u)) << 24), 4);
   } else if (X >= 0) {
-    for (int i = 0; i <= X; ++i) s.put(dg[i]);
-    if (last > X) { s.put('.'); for (int i = X + 1; i <= last; ++i) s.put(dg[i]); }
+    if (last > X) put_packed(s, gdb_packed_insert_dot(w, X + 1), last + 2); else put_packed(s, w, X + 1);
   } else {
-    s.put('0'); s.put('.');
-    for (int i = 0; i < -X - 1; ++i) s.put('0');
-    for (int i = 0; i <= last; ++i) s.put(dg[i]);
+    put_packed(s, gdb_packed_zero_dot(), 2 + (-X - 1));
+    put_packed(s, w, last + 1);
   }
 }
 
@@ -361,23 +379,37 @@ template <class Sink> GDB_HD bool put_float(Sink& s, float f) {
   if (d < 0.001) i += 5; else if (d < 0.01) i += 50; else if (d < 0.1) i += 500; else if (d < 1) i += 5000;
   else if (d < 10) i += 50000; else if (d < 100) i += 500000; else if (d < 1000) i += 5000000;
   else if (d < 10000) i += 50000000; else if (d < 100000) i += 500000000; else i += 5000000000ULL;
-  char dg[24];
-  int p = 0;
-  { char tmp[24]; int n = 0; do { tmp[n++] = (char)('0' + i % 10); i /= 10; } while (i); while (n) dg[p++] = tmp[--n]; }
-  char out[40];
-  int m = 0, dot = -1;
-  if (p <= 10) {
-    out[m++] = '0'; dot = m; out[m++] = '.';
-    for (int z = 0; z < 10 - p; ++z) out[m++] = '0';
-    int take = p < 6 ? p : 6;
-    for (int z = 0; z < take; ++z) out[m++] = dg[z];
+  // i < 10^16 (d <= 999999): split once by 10^8 into two 32-bit halves; p = number of digits of i (>= 7: d >= 0.0001), T = its
+  // first six digits.  kputd prints those six - behind "0." and 10 - p zeros when p <= 10, else with the point behind the first
+  // p - 10 of them - and removes trailing zeros behind the point, down to one digit.  All in registers: no digit array.
+  const uint64_t hi64 = i / 100000000ull;
+  const uint32_t hi = (uint32_t)hi64, lo = (uint32_t)(i - hi64 * 100000000ull);
+  uint32_t T;
+  int p;
+  if (hi) {
+    int ph = 1;
+    for (uint32_t t = hi; t >= 10u; t /= 10u) ++ph;
+    p = 8 + ph;
+    if (ph >= 6) { T = hi; for (int z = ph; z > 6; --z) T /= 10u; }
+    else { uint32_t l = lo, m = hi; for (int z = 0; z < 2 + ph; ++z) l /= 10u; for (int z = ph; z < 6; ++z) m *= 10u; T = m + l; }
   } else {
-    int ip = p - 10;
-    for (int z = 0; z < ip; ++z) out[m++] = dg[z];
-    if (ip < 6) { dot = m; out[m++] = '.'; for (int z = ip; z < 6; ++z) out[m++] = dg[z]; }
+    p = 1;
+    for (uint32_t t = lo; t >= 10u; t /= 10u) ++p;
+    T = lo;
+    for (int z = p; z > 6; --z) T /= 10u;
   }
-  if (dot >= 0) while (m > dot + 2 && out[m - 1] == '0') --m;
-  s.write(out, m);
+  int L = 6;                                               // digits of T without its trailing zeros (>= 1: the first digit is not 0)
+  { uint32_t t = T; while (L > 1) { const uint32_t t10 = t / 10u; if (t - t10 * 10u) break; t = t10; --L; } }
+  int nd = 0;
+  const uint64_t w = gdb_pack_digits(T, nd);               // nd = 6
+  if (p <= 10) {
+    put_packed(s, gdb_packed_zero_dot(), 2 + (10 - p));
+    put_packed(s, w, L);
+  } else {
+    const int ip = p - 10;
+    if (ip < 6) put_packed(s, gdb_packed_insert_dot(w, ip), ip + 1 + (L > ip ? L - ip : 1));
+    else put_packed(s, w, 6);
+  }
   return true;
 }
 
@@ -403,6 +435,24 @@ GDB_HD bool alt_token(const char* s, int len, int idx, const char*& tok, int& tl
   }
   return false;
 }
+// The same tokens in one pass over the string: next() hands out the token behind the one it returned last (a loop over
+// alt_token(idx) scans the string from its start for every idx)
+struct AltTokens {
+  const char* s;
+  int len, i;
+  int idx;     // of the token handed out last (alt_token's idx)
+  GDB_HD AltTokens(const char* s_, int len_) : s(s_), len(len_), i(0), idx(-1) {}
+  GDB_HD bool next(const char*& tok, int& tlen) {
+    while (i < len && s[i] == '|') ++i;
+    if (i >= len) return false;
+    int j = i;
+    while (j < len && s[j] != '|') ++j;
+    tok = s + i; tlen = j - i;
+    i = j;
+    ++idx;
+    return true;
+  }
+};
 GDB_HD bool allele_is_symbolic(const char* a, int n) {  // VariantUtils::is_symbolic_allele
   if (n > 0 && a[0] == '&') return true;
   if (n == 1 && a[0] == '*') return true;
@@ -441,7 +491,7 @@ GDB_HD void classify_cell(const FragmentView& fr, const CombinePlan& pl, const C
     const char* alt = cell_field<char>(fr, pl, pl.f_ALT, c, alt_len);
     bool deletion = false, has_nr = false;
     const char* tok; int tl;
-    for (int i = 0; alt_token(alt, alt_len, i, tok, tl); ++i) {
+    for (AltTokens at(alt, alt_len); at.next(tok, tl);) {
       ++nalt;
       if (tl > 0 && tok[0] == '&') has_nr = true;
       if (ref_len > 1 && !allele_is_symbolic(tok, tl) && tl < ref_len) deletion = true;  // contains_deletion
@@ -857,6 +907,9 @@ struct SiteCtx {
   TieScratch tie;
   ScalarPre pre;
   HugeSites huge;
+  // optional: [P] the lowest cell that begins at the record's start, -1 when none does (filled by the sweep that computes the
+  // cells' record ranges: stage_first_cell); null = site_first_ref searches the fragment's cells
+  const int64_t* first_cell_at;
 };
 
 // value of a scalar INFO-like field over the heavy list: median / sum / mean (variant_field_handler.cc:529-607).
@@ -1279,10 +1332,15 @@ GDB_HD int merged_find_or_add(AlleleRef* merged, int& nmerged, MergeIndex& ix, c
 }
 
 // REF of the lowest-row cell starting at s_k (cells are (col,row) sorted; a plain reference block counts), or null
-GDB_HD const char* site_first_ref(const SiteCtx& cx, int64_t s_k, int& len) {
+GDB_HD const char* site_first_ref(const SiteCtx& cx, int64_t k, int64_t s_k, int& len) {
+  len = 0;
+  if (cx.first_cell_at) {
+    const int64_t c = cx.first_cell_at[k];
+    if (c >= 0 && field_valid(cx.cm, c, cx.pl.f_REF)) return cell_field<char>(cx.fr, cx.pl, cx.pl.f_REF, c, len);
+    return nullptr;
+  }
   int64_t lo = 0, hi = cx.fr.ncells;
   while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (cx.fr.begin[mid] < s_k) lo = mid + 1; else hi = mid; }
-  len = 0;
   if (lo < cx.fr.ncells && cx.fr.begin[lo] == s_k && field_valid(cx.cm, lo, cx.pl.f_REF)) return cell_field<char>(cx.fr, cx.pl, cx.pl.f_REF, lo, len);
   return nullptr;
 }
@@ -1314,8 +1372,8 @@ template <class F> GDB_HD void site_merge_call(const SiteCtx& cx, int64_t t, int
       int lowest = -1;
       int lowest_pl = 0x7FFFFFFF;
       const char* tok; int tl;
-      for (int i = 0; alt_token(alt, alt_len, i, tok, tl); ++i) {
-        int aidx = i + 1;
+      for (AltTokens at(alt, alt_len); at.next(tok, tl);) {
+        int aidx = at.idx + 1;
         if (allele_is_deletion(ref_len, tok, tl)) {
           if (lowest < 0) lowest = aidx;
           if (pl_exists) {
@@ -1337,7 +1395,7 @@ template <class F> GDB_HD void site_merge_call(const SiteCtx& cx, int64_t t, int
       if (lut && pl.min_PL_GT_for_spanning_deletions && pl.produce_GT_field && pl_exists && pl.f_GT >= 0 && field_valid(cx.cm, c, pl.f_GT)) {
         // update_GT_to_correspond_to_min_PL_value on the REDUCED PL (alleles REF,*,[<NON_REF>])
         int nr_idx = -1;
-        for (int i = 0; alt_token(alt, alt_len, i, tok, tl); ++i) if (tl > 0 && tok[0] == '&') nr_idx = i + 1;
+        for (AltTokens at(alt, alt_len); at.next(tok, tl);) if (tl > 0 && tok[0] == '&') nr_idx = at.idx + 1;
         int red2in[3] = {0, lowest, nr_idx};
         int nred = nr_idx >= 0 ? 3 : 2;
         int best_min = 0x7FFFFFFF, best_a = -1, best_b = -1;
@@ -1377,18 +1435,20 @@ template <class F> GDB_HD void site_merge_call(const SiteCtx& cx, int64_t t, int
     } else {
       bool suffix_needed = ref_len < mref_len;
       const char* tok; int tl;
-      for (int i = 0; alt_token(alt, alt_len, i, tok, tl); ++i) {
+      for (AltTokens at(alt, alt_len); at.next(tok, tl);) {
         if (tl > 0 && tok[0] == '&') continue;  // <NON_REF> goes last
         AlleleRef cand{tok, tl, (suffix_needed && !allele_is_symbolic(tok, tl)) ? ref_len : -1, 0u};
         cand.hash = allele_hash(cand.p, cand.len, cand.suffix_from, mref, mref_len);
         const int found = find_or_add(cand);
-        if (lut && i + 1 <= nalt) lut[i + 1] = (int8_t)found;
+        if (lut && at.idx + 1 <= nalt) lut[at.idx + 1] = (int8_t)found;
       }
     }
     if (write_luts) cx.hl.iflags[t] = iflag;
 }
 
-template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& sink, bool write_luts, uint32_t* err) {
+// BCF = the flavour of the fixed columns: the BCF2 shared block (pl.bcf_mode) or VCF text.  A kernel instantiates the one it is
+// launched for, so that the text kernels carry no BCF2 emitter and the BCF2 kernels no text emitter.
+template <bool BCF, class Sink> GDB_HD void site_emit_as(const SiteCtx& cx, int64_t k, Sink& sink, bool write_luts, uint32_t* err) {
   const CombinePlan& pl = cx.pl;
   const int64_t s_k = cx.rec.start[k], e_k = cx.rec.end[k];
   const int64_t hb = cx.hl.base[k], he = cx.hl.base[k + 1];
@@ -1399,7 +1459,7 @@ template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& 
   const HugeSiteOut* hsite = (cx.huge.enabled && cx.huge.index[k] >= 0 && !cx.huge.out[cx.huge.index[k]].fallback) ? &cx.huge.out[cx.huge.index[k]] : nullptr;
   {
     if (hsite) { mref = hsite->mref; mref_len = hsite->mref_len; }
-    else mref = site_first_ref(cx, s_k, mref_len);
+    else mref = site_first_ref(cx, k, s_k, mref_len);
     if (!hsite) for (int64_t t = hb; t < he; ++t) {
       int64_t c = cx.hl.cell[t];
       if (cx.fr.begin[c] != s_k || !field_valid(cx.cm, c, pl.f_REF)) continue;
@@ -1441,8 +1501,8 @@ template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& 
       int alt_len;
       const char* alt = cell_field<char>(cx.fr, pl, pl.f_ALT, c, alt_len);
       const char* tok; int tl;
-      for (int i = 0; alt_token(alt, alt_len, i, tok, tl); ++i)
-        if (tl > 0 && tok[0] == '&' && i + 1 <= (int)GDB_CF_NALT(cf)) cx.hl.i2m[cx.hl.i2m_off[t] + i + 1] = (int8_t)(num_merged - 1);
+      for (AltTokens at(alt, alt_len); at.next(tok, tl);)
+        if (tl > 0 && tok[0] == '&' && at.idx + 1 <= (int)GDB_CF_NALT(cf)) cx.hl.i2m[cx.hl.i2m_off[t] + at.idx + 1] = (int8_t)(num_merged - 1);
     }
   }
   const bool ref_block_only = (mref_len == 1 && nmerged == 1 && non_ref_exists);
@@ -1465,7 +1525,7 @@ template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& 
   int ci = find_contig(cx.qw, s_k);
   if (ci < 0) { *err |= GDB_ERR_INTERNAL; ci = 0; }
   const GdbContig& ctg = cx.qw.contigs[ci];
-  if (pl.bcf_mode) {
+  if constexpr (BCF) {
     // BCF2 shared block (BCFv2.2 6.3.1; the order of the reference's bcf_update_* calls, broad_combined_gvcf.cc:795-880):
     // CHROM POS rlen QUAL n_allele|n_info n_fmt|n_sample ID alleles FILTER INFO...; l_shared / l_indiv and the FORMAT block
     // are written by the page assembly.  rlen = END - POS for interval records, else the length of REF.
@@ -1576,7 +1636,7 @@ template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& 
       if ((pl.f_DP >= 0 || pl.f_DP_FORMAT >= 0) && dp > 0 && !ref_block_only) { bcf_enc_int1(sink, pl.bcf_dp_id); bcf_enc_int1(sink, dp); ++n_info; }
     }
     sink.patch_u32(at_counts, ((uint32_t)num_merged << 16) | (n_info & 0xFFFFu));
-    return;
+    return;                                               // (what follows is the text flavour: unreachable, and so not emitted, here)
   }
   sink.write(cx.qw.contig_names + ctg.name_off, ctg.name_len);
   sink.put('\t');
@@ -1704,6 +1764,10 @@ template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& 
       else sink.write(cx.names.text + cx.names.field_name_off[f], cx.names.field_name_len[f]);
     }
   }
+}
+// the flavour taken from the plan (CPU harness)
+template <class Sink> GDB_HD void site_emit(const SiteCtx& cx, int64_t k, Sink& sink, bool write_luts, uint32_t* err) {
+  if (cx.pl.bcf_mode) site_emit_as<true>(cx, k, sink, write_luts, err); else site_emit_as<false>(cx, k, sink, write_luts, err);
 }
 
 // ---- sample entries --------------------------------------------------------------------------------------

@@ -143,6 +143,23 @@ GDB_HD bool stage_cell_range(const FragmentView& fr, const CellMeta& cm, const R
   if (cm.cflags[c] & GDB_CF_HEAVY) heavy_count[c - c_base] = khi - klo + 1;
   return true;
 }
+// first_cell_at[k] := the lowest cell that begins at record k's start (the table is filled with -1 beforehand: no such cell).
+// Cells are sorted by (column, row), so the first cell of a run of equal begin is the one; every cell of the window passes through
+// here once, whether it is live or not - the site pass asks for the REF of the cell at that place, whatever else holds for it.
+// Records start inside [qb, qe], and the window holds every cell that begins there.
+GDB_HD void stage_first_cell(const FragmentView& fr, const RecordTable& rec, int64_t c, int64_t qb, int64_t qe, const int32_t* first_record_at,
+                             int64_t* first_cell_at) {
+  const int64_t b = fr.begin[c];
+  if (b < qb || b > qe || (c > 0 && fr.begin[c - 1] == b)) return;
+  int64_t k;
+  if (first_record_at) k = first_record_at[b - qb];
+  else {
+    int64_t lo = 0, hi = rec.npos;
+    while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (rec.start[mid] < b) lo = mid + 1; else hi = mid; }
+    k = lo;
+  }
+  if (k < rec.npos && rec.start[k] == b) first_cell_at[k] = c;
+}
 // contribution of a cell to packed word `word` (presence of FORMAT fields / <NON_REF>)
 GDB_HD uint64_t stage_packed_word(const CombinePlan& pl, const DiffPacked& pk, uint64_t vmask, uint32_t cflags, int word) {
   uint64_t acc = 0;

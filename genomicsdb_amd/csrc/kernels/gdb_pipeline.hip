@@ -257,7 +257,7 @@ __device__ __forceinline__ uint64_t wave_run_sum(uint32_t key, uint64_t v, int l
   return v;
 }
 __global__ void k_cell_ranges(FragmentView fr, CombinePlan pl, CellMeta cm, RecordTable rec, int64_t c_base, int64_t n, int64_t qb, int64_t qe,
-                              int64_t* heavy_count, int32_t* in_window_count, const int32_t* first_record_at, DiffPacked pk) {
+                              int64_t* heavy_count, int32_t* in_window_count, const int32_t* first_record_at, DiffPacked pk, int64_t* first_cell_at) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   bool live = false;
@@ -267,6 +267,7 @@ __global__ void k_cell_ranges(FragmentView fr, CombinePlan pl, CellMeta cm, Reco
     const int64_t c = c_base + i;
     live = stage_cell_range(fr, cm, rec, c, c_base, qb, qe, heavy_count, first_record_at, klo, khi);
     if (live) { vm = cm.vmask[c]; cf = cm.cflags[c]; dp = cm.dpval[c]; } else klo = -1 - (int64_t)lane;
+    stage_first_cell(fr, rec, c, qb, qe, first_record_at, first_cell_at);   // (live or not: site_first_ref asks for the cell that BEGINS at the record)
   }
   const int64_t prev_key = __shfl_up(klo, 1, 64);
   const bool head = lane == 0 || prev_key != klo;
@@ -587,7 +588,7 @@ __global__ void __launch_bounds__(kHugeBlock) k_site_huge(const SiteCtx* __restr
     // ---- merged REF: longest REF among the calls starting here, the first one at equal length ---------------------------------
     if (tid == 0) {
       int len0 = 0;
-      s_mref = site_first_ref(cx, s_k, len0);
+      s_mref = site_first_ref(cx, k, s_k, len0);
       s_mref_len = len0;
       s_key = ((unsigned long long)(uint32_t)len0 << 32) | 0xFFFFFFFFull;
       s_flags[0] = s_flags[1] = s_flags[2] = s_flags[3] = 0;
@@ -799,10 +800,19 @@ constexpr int kSiteStride = 256;                   // distance of two records' s
 // bytes of the fixed columns that are parked in the lane's LDS strip (the rest goes to the record's tail slot in global memory, word by
 // word: LdsSpillSink).  The site pass is a latency-bound kernel of one wavefront per workgroup, and the strip is what bounds its
 // residency: 256 bytes per lane = 9 wavefronts per CU, 192 = 12 (the register limit at 149), 128 and the registers capped at 128
-// (amdgpu_waves_per_eu(4)) = 16.  c2, site phase, A/B inside one call: 2.79 (256) / 2.48 (192) / 2.53 (128) / 2.37 ms (128, capped).  Until
-// round 4 anything below ~190 bytes was a cliff (160 bytes: 9.1 ms) - c2's fixed columns are ~170 bytes at variant sites, and the tails
-// went byte by byte through a pool of 32 768 chunks handed out by one atomic counter (exhausted after a tenth of the spilling records,
-// the rest formatted a second time by the page pass).  With a tail slot per record there is no counter and no second formatting.
+// (amdgpu_waves_per_eu(4)) = 16.  The strip size was chosen on c2's site phase, A/B inside one call, with the number text still going
+// through digit buffers in private memory: 2.79 (256) / 2.48 (192) / 2.53 (128) / 2.37 ms (128, capped); the choice has not been
+// measured again since.  Until round 4 anything below ~190 bytes was a cliff (160 bytes: 9.1 ms) - c2's fixed columns are ~170 bytes at
+// variant sites, and the tails went byte by byte through a pool of 32 768 chunks handed out by one atomic counter (exhausted after a
+// tenth of the spilling records, the rest formatted a second time by the page pass).  With a tail slot per record there is no counter
+// and no second formatting.
+// What the kernel is now: one instantiation per flavour of the fixed columns (k_site_size: VCF text, k_site_size_bcf: the BCF2 shared
+// block); POS, END= and the float INFO values leave as packed 8-byte words (gdb_core.hpp put_u64 / put_float: no digit buffers), the ALT
+// strings are walked once (AltTokens), and the first cell of a record comes from the sweep's first_cell_at table instead of a binary
+// search over the fragment.  The private frame is still ~4 KB per lane (4 008 bytes for text, 3 960 for BCF2; before: 4 072): `merged[128]`
+// (3 KB) and MergeIndex (257 bytes) of site_emit_as, the ID token and FILTER union tables, and the register spills at the 128-VGPR cap
+// (45 VGPRs, 266 SGPRs for text).  A merged-allele table sized to the record (16 entries and no MergeIndex for records of at most 14 ALT
+// alleles) has been neither built nor measured.  Durations, HBM traffic and the A/B runs: profiles/site_pass.md.
 #ifndef GDBAMD_SITE_CAP
 #define GDBAMD_SITE_CAP 128
 #endif
@@ -820,7 +830,7 @@ __global__ void k_site_order_keys(const int64_t* __restrict__ hbase, int64_t P, 
 #ifndef GDBAMD_SITE_ATTR
 #define GDBAMD_SITE_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 #endif
-__global__ void __launch_bounds__(64) GDBAMD_SITE_ATTR k_site_size(const SiteCtx* __restrict__ sxp, const int32_t* __restrict__ order, char* __restrict__ staging, SpillPool spill, int32_t* __restrict__ spill_chunk, uint32_t* err) {
+template <bool BCF> __device__ __forceinline__ void site_size_body(const SiteCtx* __restrict__ sxp, const int32_t* __restrict__ order, char* __restrict__ staging, const SpillPool& spill, int32_t* __restrict__ spill_chunk, uint32_t* err) {
   const SiteCtx& sx = *sxp;
   __shared__ uint32_t strip[64 * kSiteStripWords];
   int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -829,7 +839,7 @@ __global__ void __launch_bounds__(64) GDBAMD_SITE_ATTR k_site_size(const SiteCtx
   uint32_t e = 0;
   uint32_t* mine = strip + threadIdx.x * kSiteStripWords;
   LdsSpillSink cs((gdb_lds_char*)mine, (uint32_t)kSiteCap, spill, k);
-  site_emit(sx, k, cs, true, &e);
+  site_emit_as<BCF>(sx, k, cs, true, &e);
   cs.flush();
   sx.so.prefix_len[k] = cs.n;
   // longer texts: the tail lies in a chunk of the spill pool (or, when that did not work out, the page pass formats the record again)
@@ -838,6 +848,13 @@ __global__ void __launch_bounds__(64) GDBAMD_SITE_ATTR k_site_size(const SiteCtx
   uint4* dst = reinterpret_cast<uint4*>(staging + (size_t)k * kSiteStride);
   for (uint32_t q = 0; (q << 4) < nstaged; ++q) dst[q] = make_uint4(mine[4 * q], mine[4 * q + 1], mine[4 * q + 2], mine[4 * q + 3]);
   if (e) atomicOr(err, e);
+}
+// one kernel per flavour of the fixed columns: VCF text (k_site_size) and the BCF2 shared block (k_site_size_bcf)
+__global__ void __launch_bounds__(64) GDBAMD_SITE_ATTR k_site_size(const SiteCtx* __restrict__ sxp, const int32_t* __restrict__ order, char* __restrict__ staging, SpillPool spill, int32_t* __restrict__ spill_chunk, uint32_t* err) {
+  site_size_body<false>(sxp, order, staging, spill, spill_chunk, err);
+}
+__global__ void __launch_bounds__(64) GDBAMD_SITE_ATTR k_site_size_bcf(const SiteCtx* __restrict__ sxp, const int32_t* __restrict__ order, char* __restrict__ staging, SpillPool spill, int32_t* __restrict__ spill_chunk, uint32_t* err) {
+  site_size_body<true>(sxp, order, staging, spill, spill_chunk, err);
 }
 // The parked fixed columns of a record (<= 256 bytes, 256-byte aligned staging slot) -> their place in the page, one wavefront
 // per record: lane j assembles the j-th ALIGNED destination word from its own source word and its left neighbour's
@@ -889,7 +906,7 @@ __global__ void k_site_write(const SiteCtx* __restrict__ sxp, const char* __rest
     return;                                     // head parked, tail in the spill pool: k_site_copy has put both in place
   } else {
     ByteSink bs(dst);
-    site_emit(sx, k, bs, false, &e);
+    site_emit_as<false>(sx, k, bs, false, &e);
   }
   arena[chunk_off[(k + 1) * nchunks] - page_base - 1] = '\n';
   if (e) atomicOr(err, e);
@@ -2871,7 +2888,7 @@ __global__ void k_bcf_shared(const SiteCtx* __restrict__ sxp, const char* __rest
     for (uint32_t i = kSiteCap; i < n; ++i) dst[i] = tail[i - kSiteCap];
   } else {
     ByteSink bs(dst);
-    site_emit(sx, k, bs, false, &e);
+    site_emit_as<true>(sx, k, bs, false, &e);
   }
   const uint32_t mask = sx.so.fmt_mask[k];
   int q = 0;
@@ -3763,7 +3780,7 @@ struct DevicePipeline::Impl {
   DevBuf<uint64_t> ev_keys, ev_keys_sorted; DevBuf<int64_t> ev_delta, ev_incl; DevBuf<int32_t> run_end, run_excl;
   DevBuf<int64_t> bpos, bnrec, rbase; DevBuf<int32_t> bcov, bdel;
   DevBuf<int64_t> rstart, rend;
-  DevBuf<int32_t> diff, first_record_at; DevBuf<uint64_t> diff_packed; DevBuf<int64_t> heavy_count, hoff;
+  DevBuf<int32_t> diff, first_record_at; DevBuf<uint64_t> diff_packed; DevBuf<int64_t> heavy_count, hoff, first_cell_at;
   DevBuf<uint64_t> inc_keys, inc_keys_sorted; DevBuf<int64_t> inc_vals, inc_vals_sorted, hbase;
   DevBuf<uint32_t> lut_len, i2m_off; DevBuf<int8_t> i2m, gt_override; DevBuf<uint8_t> iflags;
   DevBuf<uint8_t> num_alleles, rflags; DevBuf<uint32_t> fmt_mask, prefix_len; DevBuf<char> site_staging, spill_buf; DevBuf<int32_t> spill_chunk;
@@ -5413,8 +5430,11 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     }
     first_record_at = S.first_record_at.p;
   }
+  // the lowest cell beginning at each record's start (-1: none), for the site pass: written by the same sweep
+  S.first_cell_at.ensure((size_t)P);
+  HIP_CHECK(hipMemsetAsync(S.first_cell_at.p, 0xFF, (size_t)P * sizeof(int64_t), st));
   STAGE("k_cell_ranges");
-  hipLaunchKernelGGL(k_cell_ranges, dim3(blocks_for(CW)), dim3(kBlock), 0, st, fr, pl, cm, rec, c_base, CW, qb, qe, S.heavy_count.p, S.counters.p, first_record_at, pk);
+  hipLaunchKernelGGL(k_cell_ranges, dim3(blocks_for(CW)), dim3(kBlock), 0, st, fr, pl, cm, rec, c_base, CW, qb, qe, S.heavy_count.p, S.counters.p, first_record_at, pk, S.first_cell_at.p);
   // every difference array sums to zero over its P+1 elements, so ONE scan over the concatenation equals separate scans
   S.incl_scan(pk.w, pk.w, (size_t)pk.nwords * stride, rocprim::plus<uint64_t>());
   hipLaunchKernelGGL(k_unpack_counts, dim3(blocks_for(stride)), dim3(kBlock), 0, st, pk, nf, stride, da);
@@ -5541,7 +5561,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   // records with very many variant calls: their call walk is done by one workgroup each, before the per-thread site pass
   HugeSites huge;
   memset(&huge, 0, sizeof(huge));
-  SiteCtx sx0{fr, pl, cm, rec, hl, pc, nt, qw, so, med, big, tie, pre, huge};
+  SiteCtx sx0{fr, pl, cm, rec, hl, pc, nt, qw, so, med, big, tie, pre, huge, S.first_cell_at.p};
   // Which records get a workgroup of their own: the ones with more than kHugeRecord variant calls - and, when the interval's records
   // carry many calls on average (tens of thousands of samples: BASELINE configs[4] has ~100 calls on every record and a few
   // thousand records per piece, i.e. a few dozen wavefronts of one-thread-per-record walks of 100 calls each), every record with
@@ -5555,7 +5575,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
     hipLaunchKernelGGL(k_site_huge, dim3(1024), dim3(kHugeBlock), 0, st, (const SiteCtx*)S.d_sx0.p, (const int32_t*)S.huge_list.p, (const int32_t*)(S.counters.p + 3), S.huge_out.p, S.err.p, S.counters.p + 6);
     huge.index = S.huge_index.p; huge.out = S.huge_out.p; huge.enabled = 1;
   }
-  SiteCtx sx{fr, pl, cm, rec, hl, pc, nt, qw, so, med, big, tie, pre, huge};
+  SiteCtx sx{fr, pl, cm, rec, hl, pc, nt, qw, so, med, big, tie, pre, huge, S.first_cell_at.p};
   S.d_sx.ensure(1);
   HIP_CHECK(hipMemcpyAsync(S.d_sx.p, &sx, sizeof(SiteCtx), hipMemcpyHostToDevice, st));   // (sx outlives the copy: the function synchronises before it returns)
   STAGE("k_site_size");
@@ -5571,7 +5591,8 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
       site_order = S.site_ord.p;
     }
   }
-  hipLaunchKernelGGL(k_site_size, dim3(blocks_for(P, 64)), dim3(64), 0, st, S.d_sx.p, site_order, S.site_staging.p, SpillPool{S.spill_buf.p}, S.spill_chunk.p, S.err.p);
+  if (pl.bcf_mode) hipLaunchKernelGGL(k_site_size_bcf, dim3(blocks_for(P, 64)), dim3(64), 0, st, S.d_sx.p, site_order, S.site_staging.p, SpillPool{S.spill_buf.p}, S.spill_chunk.p, S.err.p);
+  else hipLaunchKernelGGL(k_site_size, dim3(blocks_for(P, 64)), dim3(64), 0, st, S.d_sx.p, site_order, S.site_staging.p, SpillPool{S.spill_buf.p}, S.spill_chunk.p, S.err.p);
   S.remap_total.ensure(1);
   HIP_CHECK(hipMemsetAsync(S.remap_total.p, 0, sizeof(unsigned long long), st));
   for (int i = 0; i < pl.n_format; ++i)
