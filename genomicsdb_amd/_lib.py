@@ -33,6 +33,13 @@ class StreamStats(ctypes.Structure):
                 ("seconds_waiting_for_copies", ctypes.c_double), ("seconds_producing", ctypes.c_double)]
 
 
+class OutputIndexStats(ctypes.Structure):
+    """gdb_mi355_index_stats of include/genomicsdb_amd.h"""
+    _fields_ = [("pages", ctypes.c_int64), ("records", ctypes.c_int64), ("contigs", ctypes.c_int64), ("bins", ctypes.c_int64), ("chunks", ctypes.c_int64),
+                ("linear_windows", ctypes.c_int64), ("atomics", ctypes.c_int64), ("ms_records", ctypes.c_double), ("ms_voff", ctypes.c_double),
+                ("ms_chunks", ctypes.c_double), ("ms_linear", ctypes.c_double), ("s_write", ctypes.c_double), ("table_bytes", ctypes.c_uint64)]
+
+
 class DeviceColumn(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("off", ctypes.c_void_p)]
 
@@ -53,7 +60,7 @@ SYMBOLS = ["gdb_mi355_last_error", "gdb_mi355_device_count", "gdb_mi355_init", "
            "gdbamd_importer_import_batch", "gdbamd_importer_is_done", "gdbamd_importer_finish", "gdbamd_importer_stats", "gdbamd_importer_destroy",
            "gdbamd_chromosome_intervals_for_column_partition", "gdbamd_input_histogram", "gdbamd_histogram_text", "gdbamd_vcfdiff",
            "gdbamd_index_vcf_device", "gdbamd_split_files_device_index", "gdbamd_merge_cell_files",
-           "gdbamd_engine_columns_select", "gdbamd_engine_page_columns"]
+           "gdbamd_engine_columns_select", "gdbamd_engine_page_columns", "gdb_mi355_enable_index", "gdb_mi355_write_index"]
 
 
 class HistogramStats(ctypes.Structure):
@@ -146,6 +153,8 @@ def lib():
     L.gdb_mi355_read.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint64]
     L.gdb_mi355_peek.argtypes = [c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_uint64)]
     L.gdb_mi355_get_stream_stats.argtypes = [c.c_void_p, c.POINTER(StreamStats)]
+    L.gdb_mi355_enable_index.argtypes = [c.c_void_p]
+    L.gdb_mi355_write_index.argtypes = [c.c_void_p, c.c_char_p, c.POINTER(OutputIndexStats)]
     L.gdb_mi355_skip.restype = c.c_int64
     L.gdb_mi355_skip.argtypes = [c.c_void_p, c.c_uint64]
     L.gdbamd_engine_create.restype = c.c_void_p

@@ -40,8 +40,21 @@ class GenomicsDBQueryStream:
 
     def __init__(self, loader_json_file=None, query_json_file=None, chr="", start=0, end=0, rank=0, buffer_capacity=1048576,
                  segment_size=1048576, is_bcf=False, produce_header_only=False, query_json=None, cells=None,
-                 use_missing_values_only_not_vector_end=False, keep_idx_fields_in_bcf_header=True, output_format=None):
-        """output_format (the reference's vcf_output_format: "", "bu", "z", "b") overrides is_bcf when given"""
+                 use_missing_values_only_not_vector_end=False, keep_idx_fields_in_bcf_header=True, output_format=None, index=False):
+        """output_format (the reference's vcf_output_format: "", "bu", "z", "b") overrides is_bcf when given.
+        index=True ("z" / "b" only): the .tbi / .csi of the stream's bytes is built on the device while the pages are
+        there; write_index(path) writes it once the stream has been read to its end"""
+        self._open(loader_json_file, query_json_file, chr, start, end, rank, buffer_capacity, segment_size, is_bcf, produce_header_only, query_json, cells,
+                   use_missing_values_only_not_vector_end, keep_idx_fields_in_bcf_header, output_format)
+        if index:
+            try:
+                self.enable_index()
+            except Exception:
+                self.close()
+                raise
+
+    def _open(self, loader_json_file, query_json_file, chr, start, end, rank, buffer_capacity, segment_size, is_bcf, produce_header_only, query_json, cells,
+              use_missing_values_only_not_vector_end, keep_idx_fields_in_bcf_header, output_format):
         L = _lib.lib()
         if output_format is not None:
             fmt = output_format.encode()
@@ -104,6 +117,19 @@ class GenomicsDBQueryStream:
         st = _lib.StreamStats()
         _check(_lib.lib().gdb_mi355_get_stream_stats(self._h, ctypes.byref(st)) == 0, "stream_stats")
         return st
+
+    def enable_index(self):
+        """build the index of the stream's bytes on the device ("z" / "b" only, before the header has been read to its end)"""
+        if _lib.lib().gdb_mi355_enable_index(self._h) != 0:
+            raise GenomicsDBException("enable_index: " + _lib.last_error())
+
+    def write_index(self, path):
+        """the .tbi ("z") / .csi ("b") of the bytes this stream has handed out, to `path`; only once the stream has been read
+        to its end.  -> dict of gdb_mi355_index_stats"""
+        st = _lib.OutputIndexStats()
+        if _lib.lib().gdb_mi355_write_index(self._h, os.fsencode(path), ctypes.byref(st)) != 0:
+            raise GenomicsDBException("write_index: " + _lib.last_error())
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     def skip(self, n):
         return _lib.lib().gdb_mi355_skip(self._h, n)

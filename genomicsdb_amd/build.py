@@ -6,6 +6,7 @@ repo snapshot to the GPU box.  Also builds the test oracle (oracle/Makefile) and
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -26,6 +27,7 @@ SOURCES = [
     "kernels/gdb_split.hip",
     "kernels/gdb_histogram.hip",
     "kernels/gdb_index.hip",
+    "kernels/gdb_output_index.hip",
     "kernels/gdb_vcfdiff.hip",
     "kernels/gdb_columns.hip",
     "host/vid_mapper.cc",
@@ -64,16 +66,23 @@ def _newer(target, deps):
 def build_native(verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hdrs = _headers()
-    objs = []
+    objs, stale = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         objs.append(obj)
         if _newer(obj, [src] + hdrs):
-            cmd = [HIPCC] + FLAGS + (["-x", "hip"] if s.endswith(".hip") else []) + ["-c", src, "-o", obj]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
+            stale.append([HIPCC] + FLAGS + (["-x", "hip"] if s.endswith(".hip") else []) + ["-c", src, "-o", obj])
+
+    def compile_one(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+
+    # the translation units are independent: a few at a time (MAX_JOBS, else up to 8, never more than the machine has)
+    jobs = max(1, min(int(os.environ.get("MAX_JOBS", "8")), os.cpu_count() or 1, len(stale) or 1))
+    with ThreadPoolExecutor(jobs) as pool:
+        list(pool.map(compile_one, stale))
     if _newer(LIB, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lz"]
         if verbose:
@@ -204,6 +213,15 @@ def build_hostsim_index():
     d = os.path.join(ROOT, "tests", "hostsim_index")
     subprocess.check_call(["make", "-s", "-C", d])
     return os.path.join(d, "libhostsim_index.so"), os.path.join(d, "hostsim_index")
+
+
+def build_hostsim_output_index():
+    """CPU harness around the bodies of the device builder of the output's index (core/gdb_output_index.hpp) with the shared page
+    merger and serialisers, and the same source as a stand-alone program built with the address and undefined-behaviour sanitizers
+    (tests only); -> (library, program)"""
+    d = os.path.join(ROOT, "tests", "hostsim_output_index")
+    subprocess.check_call(["make", "-s", "-C", d])
+    return os.path.join(d, "libhostsim_output_index.so"), os.path.join(d, "hostsim_output_index")
 
 
 def build_hostsim_vcfdiff():

@@ -112,6 +112,23 @@ int gdb_mi355_get_stream_stats(void* h, gdb_mi355_stream_stats* out) {
   return 0;
 }
 
+int gdb_mi355_enable_index(void* h) {
+  if (!h) return -1;
+  return guarded([&]() -> int { ((GenomicsDBBCFGenerator*)h)->enable_output_index(); return 0; }, -1);
+}
+int gdb_mi355_write_index(void* h, const char* path, gdb_mi355_index_stats* stats) {
+  if (!h || !path) return -1;
+  return guarded([&]() -> int {
+    const OutputIndexStats& s = ((GenomicsDBBCFGenerator*)h)->write_output_index(path);
+    if (stats) {
+      stats->pages = s.pages; stats->records = s.records; stats->contigs = s.contigs; stats->bins = s.bins; stats->chunks = s.chunks; stats->linear_windows = s.linear_windows;
+      stats->atomics = s.atomics; stats->ms_records = s.ms_records; stats->ms_voff = s.ms_voff; stats->ms_chunks = s.ms_chunks; stats->ms_linear = s.ms_linear;
+      stats->s_write = s.s_write; stats->table_bytes = s.table_bytes;
+    }
+    return 0;
+  }, -1);
+}
+
 void* gdbamd_engine_create(const char* query_json_text, int device) {
   return guarded([&]() -> void* { auto* e = new EngineHandle; e->eng.reset(new CombineEngine(mini_json::parse(query_json_text), device)); return e; }, (void*)nullptr);
 }

@@ -1,6 +1,7 @@
 #include "genomicsdb_bcf_generator.h"
 #include <functional>
 #include <map>
+#include <set>
 #include "../kernels/gdb_bgzf.h"
 
 #include <hip/hip_runtime_api.h>
@@ -600,7 +601,9 @@ void GenomicsDBBCFGenerator::common_init(bool produce_header_only, bool keep_idx
   if (m_engine->plan().bgzf) {
     // "z" / "b": the header is a BGZF block of its own (zlib on the host, a few KB); the body follows as blocks compressed on the
     // device; the empty EOF block ends the stream (SAM specification 4.1.2; htslib's bgzf_close writes it)
+    m_plain_header = h;
     h = bgzf_compress_host(h);
+    m_bgzf_header_bytes = h.size();
     if (produce_header_only) h.append((const char*)kBgzfEofBlock, sizeof(kBgzfEofBlock));
     else m_trailer.assign((const char*)kBgzfEofBlock, sizeof(kBgzfEofBlock));
   }
@@ -617,10 +620,51 @@ void GenomicsDBBCFGenerator::common_init(bool produce_header_only, bool keep_idx
 
 GenomicsDBBCFGenerator::~GenomicsDBBCFGenerator() {
   if (m_copy_stream) (void)hipStreamSynchronize((hipStream_t)m_copy_stream);
+  m_indexer.reset();   // (waits for the pipelines' streams, which the engine owns)
   for (auto& s : m_ring) { if (s.done) (void)hipEventDestroy((hipEvent_t)s.done); if (s.host) (void)hipHostFree(s.host); }
   m_engine.reset();   // (the pipeline synchronises its stream before it lets go of the arenas the events refer to)
   for (auto& e : m_arena_read) if (e) (void)hipEventDestroy((hipEvent_t)e);
   if (m_copy_stream) (void)hipStreamDestroy((hipStream_t)m_copy_stream);
+}
+
+void GenomicsDBBCFGenerator::enable_output_index() {
+  if (m_indexer) return;
+  if (!m_engine->plan().bgzf) throw GenomicsDBJNIException("enable_output_index: the stream is not BGZF-compressed (output format \"z\" or \"b\"): there is no file position to index");
+  if (m_body_begun) throw GenomicsDBJNIException("enable_output_index: the first body page has been produced already; enable the index before the header is read to its end");
+  const bool bcf = m_engine->plan().plan.bcf_mode != 0;
+  // the header's contigs in order: the names a text record's CHROM is looked up in; their count is the .csi's n_ref (build_csi_index counts "##contig=")
+  std::vector<std::string> contigs;
+  int64_t header_lines = 0;
+  if (bcf) {
+    size_t n_ref = 0;
+    for (size_t p = 0; (p = m_plain_header.find("##contig=", p)) != std::string::npos; ++p) ++n_ref;
+    contigs.assign(n_ref, std::string());
+  } else {
+    std::set<std::string> seen;
+    for (size_t p = 0; p < m_plain_header.size();) {
+      size_t e = m_plain_header.find('\n', p);
+      if (e == std::string::npos) e = m_plain_header.size();
+      ++header_lines;
+      if (m_plain_header.compare(p, 9, "##contig=") == 0) {
+        const size_t idp = m_plain_header.find("<ID=", p);
+        if (idp != std::string::npos && idp < e) {
+          size_t ide = m_plain_header.find_first_of(",>\n", idp + 4);
+          if (ide == std::string::npos || ide > e) ide = e;
+          const std::string id = m_plain_header.substr(idp + 4, ide - idp - 4);
+          if (seen.insert(id).second) contigs.push_back(id);
+        }
+      }
+      p = e + 1;
+    }
+  }
+  m_indexer.reset(new DeviceOutputIndexer(bcf, contigs, m_bgzf_header_bytes, header_lines));
+}
+
+const OutputIndexStats& GenomicsDBBCFGenerator::write_output_index(const std::string& path) {
+  if (!m_indexer) throw GenomicsDBJNIException("write_output_index: the index was not enabled for this stream (enable_output_index)");
+  if (!end()) throw GenomicsDBJNIException("write_output_index: the stream has not been read to its end; the offset behind its last record is not known yet");
+  m_indexer->write(path);
+  return m_indexer->st;
 }
 
 int64_t GenomicsDBBCFGenerator::max_window_columns() const {
@@ -642,6 +686,7 @@ uint64_t GenomicsDBBCFGenerator::device_page_bytes() const {
 // Makes m_page the next page of the stream (kernels complete) and starts the assembly of the one behind it.
 bool GenomicsDBBCFGenerator::advance_page() {
   if (m_done) return false;
+  m_body_begun = true;
   // (m_engine->pipeline() is looked up at every use: cover() may swap the engine's two pipelines - overlapped staging)
   VariantQueryConfig& qc = m_engine->query_config();
   const unsigned nint = std::max(1u, qc.get_num_column_intervals());
@@ -674,6 +719,7 @@ bool GenomicsDBBCFGenerator::advance_page() {
       m_interval_end = qe;
       m_interval_active = true;
     }
+    if (m_indexer) m_engine->pipeline().set_page_index_sink(m_indexer.get());   // (whichever of the engine's two pipelines it is now)
     if (m_engine->pipeline().begin_page(page_cap, m_arena_toggle, &m_page)) { m_arena_toggle ^= 1; have = true; }
     else {
       m_interval_active = false;
@@ -683,9 +729,12 @@ bool GenomicsDBBCFGenerator::advance_page() {
   }
   m_engine->pipeline().finish_page(m_page);
   m_page_owner = &m_engine->pipeline();
+  // the page's chunks and windows join the index before the next page is begun: its records look at the contig this page ended in
+  if (m_indexer && m_page.nbytes) m_indexer->merge_page(m_page.arena, m_page.nbytes);
   // the page behind it goes into the other arena while this one drains (pages of the next piece follow once this piece is done:
   // prepare_interval needs the host)
   if (m_interval_active) {
+    if (m_indexer) m_engine->pipeline().set_page_index_sink(m_indexer.get());
     if (m_engine->pipeline().begin_page(page_cap, m_arena_toggle, &m_next_page)) { m_arena_toggle ^= 1; m_next_valid = true; }
     else {
       m_interval_active = false;

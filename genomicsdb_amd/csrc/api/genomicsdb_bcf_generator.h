@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../kernels/gdb_pipeline.h"
+#include "../kernels/gdb_output_index.h"
 #include "../host/reference_genome.h"
 
 namespace genomicsdb_amd {
@@ -169,7 +170,19 @@ class GenomicsDBBCFGenerator {
   struct DrainStats { uint64_t pages = 0, chunks = 0, bytes = 0; double seconds_waiting_for_copies = 0, seconds_producing = 0; };
   const DrainStats& drain_stats() const { return m_drain; }
   CombineEngine& engine() { return *m_engine; }   // (gt_mpi_gather --produce-histogram counts the array's cells through it)
+  // The index of the stream's bytes as a file (.tbi for "z", .csi for "b"), built on the device from every page while it is in HBM
+  // (kernels/gdb_output_index.h): the file build_tbi_index / build_csi_index write for the finished file, without re-reading it.
+  // enable_output_index(): only for a BGZF stream (plan().bgzf) and only before the first body page is produced (the header has not
+  // been read to its end).  write_output_index(path): only once end() is true.  Misuse throws GenomicsDBJNIException, which says
+  // which condition failed, and leaves the stream as it was.  A header-only stream gives the index of zero records
+  void enable_output_index();
+  const OutputIndexStats& write_output_index(const std::string& path);
+  bool output_index_enabled() const { return m_indexer != nullptr; }
  private:
+  std::unique_ptr<DeviceOutputIndexer> m_indexer;   // file position, the last contig and the merge of the pages belong to the stream, not to a pipeline: the engine swaps its two
+  uint64_t m_bgzf_header_bytes = 0;                 // compressed bytes of the header block(s), the EOF block not counted
+  std::string m_plain_header;                       // the header before compression (BGZF streams only)
+  bool m_body_begun = false;                        // advance_page has been called
   void common_init(bool produce_header_only, bool keep_idx_fields_in_bcf_header = true);
   // Stream machinery: the device assembles pages of up to device_page_bytes() (independent of the caller's buffer_capacity)
   // alternately into two HBM arenas; a page leaves in chunks over a copy stream into a ring of pinned host buffers while the

@@ -203,6 +203,47 @@ uint64_t TbiBatchMerger::num_bins() const { uint64_t n = 0; for (const TbiRef& r
 uint64_t TbiBatchMerger::num_chunks() const { uint64_t n = 0; for (const TbiRef& r : refs) for (const auto& b : r.bins) n += b.second.size(); return n; }
 uint64_t TbiBatchMerger::num_windows() const { uint64_t n = 0; for (const TbiRef& r : refs) n += r.linear.size(); return n; }
 
+OutputIndexMerger::OutputIndexMerger(bool bcf_, const std::vector<std::string>& header_contigs, uint64_t header_bytes) : bcf(bcf_), contigs(header_contigs), file_base(header_bytes) {
+  if (header_bytes == 0) throw std::runtime_error("index: an output stream without a header block");
+  if (bcf) merger.refs.resize(contigs.size());
+}
+void OutputIndexMerger::add_page(gdbidx::IdxChunk* chunks, size_t n, uint64_t page_vend, const uint32_t* win_off, const uint32_t* extent, const uint64_t* win, uint64_t compressed_bytes) {
+  const uint64_t vbase = file_base << 16;
+  merger.resolve_pending(vbase);      // the last record of the page in front ends where this page begins
+  // text: the .tbi's ids follow first appearance.  A contig's first chunk of the page holds its first record
+  std::vector<uint32_t> tid_of(contigs.size(), ~0u);
+  if (bcf) { for (size_t k = 0; k < contigs.size(); ++k) tid_of[k] = (uint32_t)k; }
+  else {
+    std::vector<std::pair<uint64_t, uint32_t>> firsts;
+    for (size_t i = 0; i < n; ++i) if (chunks[i].flags & gdbidx::IDX_CHUNK_FIRST) firsts.emplace_back(chunks[i].beg, chunks[i].tid);
+    std::sort(firsts.begin(), firsts.end());
+    for (const auto& f : firsts) { if (f.second >= contigs.size()) throw std::runtime_error("index: a chunk of a contig the header does not name"); tid_of[f.second] = merger.id_of(contigs[f.second]); }
+  }
+  uint64_t last_end = 0;
+  for (size_t i = 0; i < n; ++i) {
+    gdbidx::IdxChunk& c = chunks[i];
+    if (c.tid >= contigs.size() || tid_of[c.tid] == ~0u) throw std::runtime_error("index: a chunk of a contig the header does not name");
+    if (c.end >= last_end) { last_end = c.end; last_kid = c.tid; }
+    c.tid = tid_of[c.tid];
+    c.beg += vbase;
+    c.end = c.end == page_vend ? TbiBatchMerger::kPendingVoff : c.end + vbase;
+  }
+  merger.add_chunks(chunks, n);
+  std::vector<uint64_t> w;
+  for (size_t k = 0; k < contigs.size(); ++k) {
+    if (!extent[k] || tid_of[k] == ~0u) continue;
+    w.assign(win + win_off[k], win + win_off[k] + extent[k]);
+    for (uint64_t& v : w) if (v != ~0ull) v += vbase;
+    merger.add_windows(tid_of[k], w.data(), w.size());
+  }
+  file_base += compressed_bytes;
+}
+void OutputIndexMerger::write(const std::string& path) {
+  merger.resolve_pending((file_base + sizeof(kBgzfEofBlock)) << 16);
+  if (bcf) write_csi_index(path, merger.refs, (int)contigs.size());
+  else merger.write(path);
+}
+
 void build_tbi_index(const std::string& path) {
   BgzfReader in(path);
   std::vector<RefIndex> refs;
@@ -266,6 +307,11 @@ void build_csi_index(const std::string& path) {
     const uint64_t vend = in.tell();
     note_record(refs, chrom, pos, (int64_t)pos + std::max(1, rlen), vbeg, vend);
   }
+  write_csi_index(path + ".csi", refs, n_ref);
+}
+
+// the serialising half of both .csi builders: fill_linear (the per-bin loffset comes from the linear index), the CSIv1 layout, BGZF
+void write_csi_index(const std::string& csi_path, std::vector<TbiRef>& refs, int n_ref) {
   if ((int)refs.size() < n_ref) refs.resize((size_t)n_ref);
   fill_linear(refs);
   std::string o;
@@ -284,7 +330,7 @@ void build_csi_index(const std::string& path) {
     if (r.n_mapped) { put<uint32_t>(o, kMetaBin); put<uint64_t>(o, 0); put<int32_t>(o, 2); put<uint64_t>(o, r.off_beg); put<uint64_t>(o, r.off_end); put<uint64_t>(o, r.n_mapped); put<uint64_t>(o, 0); }
   }
   put<uint64_t>(o, 0);
-  write_bgzf(path + ".csi", o);
+  write_bgzf(csi_path, o);
 }
 
 }  // namespace genomicsdb_amd

@@ -31,6 +31,10 @@ struct TbiRef {
 // the serialising half of a .tbi builder: empty windows filled (fill_linear), the byte layout, BGZF; refs[i] belongs to names[i]
 void write_tbi_index(const std::string& tbi_path, const std::vector<std::string>& names, std::vector<TbiRef>& refs);
 
+// the serialising half of a .csi builder: refs grows to n_ref contigs (the count of ##contig lines of the BCF header), then as above
+// with the CSIv1 layout (min_shift 14, depth 5, per-bin loffset derived from the linear index)
+void write_csi_index(const std::string& csi_path, std::vector<TbiRef>& refs, int n_ref);
+
 // the words of a refused record (IDX_ERR_* bits of core/gdb_index.hpp): they name the file and the 1-based line
 std::string tbi_record_error(uint32_t bits, const std::string& path, int64_t line);
 
@@ -55,6 +59,26 @@ struct TbiBatchMerger {
   uint64_t num_chunks() const;
   uint64_t num_windows() const;
   void write(const std::string& tbi_path) { write_tbi_index(tbi_path, names, refs); }
+};
+
+// The pages of one BGZF output stream ("z": .tbi, "b": .csi), joined in stream order; what the device builder of the output's index
+// (kernels/gdb_output_index.h) and its CPU harness share.  A page brings its chunks and window minima with PAGE-RELATIVE virtual offsets
+// and with contigs named by their position among the header's ##contig IDs; here the page's file offset is added, text contigs get the
+// .tbi's ids (first appearance), and the vend of a page's last record stays pending until the next page or write() says where it is.
+struct OutputIndexMerger {
+  // header_contigs: the IDs of the header's ##contig lines in order; header_bytes: compressed bytes in front of the first page (> 0)
+  OutputIndexMerger(bool bcf, const std::vector<std::string>& header_contigs, uint64_t header_bytes);
+  // chunks: those of one contig in file order, tid = header position; page_vend: the page-relative virtual offset behind the page (the
+  // vend of its last record).  Contig k's minima are win[win_off[k] .. + extent[k]) (~0: no record).  compressed_bytes: the page's size in the file
+  void add_page(gdbidx::IdxChunk* chunks, size_t n_chunks, uint64_t page_vend, const uint32_t* win_off, const uint32_t* extent, const uint64_t* win, uint64_t compressed_bytes);
+  // the stream has ended: the 28-byte EOF block follows the last page
+  void write(const std::string& path);
+  uint32_t last_contig() const { return last_kid; }      // header position of the contig of the last record so far (~0u: none)
+  bool bcf;
+  std::vector<std::string> contigs;
+  uint64_t file_base;
+  uint32_t last_kid = ~0u;
+  TbiBatchMerger merger;
 };
 
 // <path>.tbi for a bgzip'ed VCF (records indexed by CHROM, POS and INFO END= / the REF allele's length, as tabix does for its VCF preset)

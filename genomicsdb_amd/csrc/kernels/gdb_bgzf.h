@@ -55,6 +55,10 @@ class BgzfDeviceCompressor {
   void cancel(int slot);
   // the hipEvent_t recorded behind the slot's last job (nullptr: none yet): for a producer that reuses the job's buffers from ANOTHER stream
   void* done_event(int slot) const;
+  // read-only: the compressed offset of every block of the slot's last job inside its output (device pointer, *nblocks + 1 entries, the
+  // last one the size of the output; nullptr: no job yet).  Written by the job's kernels; the slots share the table, so it holds the
+  // job's values only for work queued on the job's stream before the next enqueue() of either slot
+  const uint64_t* block_offsets(int slot, uint64_t* nblocks) const;
   struct Impl;
  private:
   Impl* m_;

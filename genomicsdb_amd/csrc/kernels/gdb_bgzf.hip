@@ -911,7 +911,7 @@ struct BgzfDeviceCompressor::Impl {
   void* temp = nullptr; size_t temp_cap = 0;
   // two jobs may be queued behind each other on one stream (the stream's two page arenas); they share the scratch buffers -
   // stream order keeps them apart - and have their own events and their own pinned word for the size of the result
-  struct Job { hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr; bool pending = false, used = false; } job[2];
+  struct Job { hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr; bool pending = false, used = false; uint64_t nblocks = 0; } job[2];
   uint64_t* h_total = nullptr;          // pinned, [2]
   void release() {
     for (void* p : {(void*)d_slice, (void*)d_shift, (void*)d_shift256, (void*)d_text_code, (void*)slots, (void*)csize, (void*)coff, (void*)crc, (void*)bsize, (void*)boff, temp}) if (p) (void)hipFree(p);
@@ -1011,7 +1011,7 @@ void BgzfDeviceCompressor::enqueue(int slot, const char* dev_src, uint64_t n, ch
   BGZF_HIP(hipEventRecord(J.ev1, st));
   BGZF_HIP(hipMemcpyAsync(S.h_total + slot, S.boff + nblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   BGZF_HIP(hipEventRecord(J.done, st));
-  J.pending = true; J.used = true;
+  J.pending = true; J.used = true; J.nblocks = nblocks;
 }
 
 void BgzfDeviceCompressor::set_text(bool pages_are_vcf_text) { m_->text = pages_are_vcf_text; }
@@ -1030,6 +1030,11 @@ uint64_t BgzfDeviceCompressor::finish(int slot, float* ms_kernels) {
 
 void BgzfDeviceCompressor::cancel(int slot) { m_->job[slot & 1].pending = false; }
 void* BgzfDeviceCompressor::done_event(int slot) const { return m_->job[slot & 1].used ? (void*)m_->job[slot & 1].done : nullptr; }
+const uint64_t* BgzfDeviceCompressor::block_offsets(int slot, uint64_t* nblocks) const {
+  const Impl::Job& J = m_->job[slot & 1];
+  if (nblocks) *nblocks = J.used ? J.nblocks : 0;
+  return J.used ? m_->boff : nullptr;
+}
 
 uint64_t BgzfDeviceCompressor::compress(const char* dev_src, uint64_t n, char* dev_dst, void* hip_stream, float* ms_kernels) {
   if (ms_kernels) *ms_kernels = 0;

@@ -158,6 +158,16 @@ class DevicePipeline {
   // the column decoder (kernels/gdb_columns.h) reads.  valid = false: no page yet
   struct PageView { bool valid = false; int64_t first = 0, last = 0; uint64_t base = 0; const uint64_t* rec_off = nullptr; const char* page = nullptr; uint64_t nbytes = 0; };
   PageView last_page() const;
+  // "z" / "b" only, opt-in: who wants to see every page of begin_page() in HBM before it is deflated in place, and the compressor's
+  // block offsets behind the deflate (kernels/gdb_output_index.h builds the output's index from them).  Both calls only queue work
+  // on `stream` (the hipStream_t of the page's kernels).  d_boff: nblocks + 1 compressed offsets inside the page, valid for work
+  // queued before the next page is begun.  nullptr (the default): nobody
+  struct PageIndexSink {
+    virtual ~PageIndexSink() {}
+    virtual void page_records(int arena, const PageView& page, void* stream) = 0;
+    virtual void page_blocks(int arena, const uint64_t* d_boff, uint64_t nblocks, uint32_t block_input, void* stream) = 0;
+  };
+  void set_page_index_sink(PageIndexSink* sink);
   // the staged fragment as device pointers (owned by this pipeline: valid until it stages, loads or adopts another one) and a counter
   // of the fragments held so far - what a second pipeline needs to work on the same fragment (adopt_fragment; CombineEngine::run_intervals)
   FragmentView fragment_view() const;

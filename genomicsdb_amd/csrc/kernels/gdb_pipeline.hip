@@ -3786,6 +3786,7 @@ struct DevicePipeline::Impl {
   DevBuf<uint8_t> num_alleles, rflags; DevBuf<uint32_t> fmt_mask, prefix_len; DevBuf<char> site_staging, spill_buf; DevBuf<int32_t> spill_chunk;
   DevBuf<uint64_t> chunk_size, chunk_off, rec_off; DevBuf<unsigned long long> max_record;
   std::unique_ptr<BgzfDeviceCompressor> bgzf;   // output formats "z" / "b"
+  DevicePipeline::PageIndexSink* index_sink = nullptr;   // set_page_index_sink
   // "z" / "b": the compression of a page is queued right behind the kernels that assemble it (finish_page only collects the size),
   // so the device works on page k + 1 - assembly and compression - while the host hands out page k.  (Round 6 measured the compression on a
   // stream of its own, beside the assembly of the next page: slower - 5.2-5.4 against 5.7-5.9 M positions/s for "z" - the two compete for the
@@ -5973,7 +5974,16 @@ bool DevicePipeline::begin_page(uint64_t arena_bytes, int arena_idx, PageTicket*
   HIP_CHECK(hipEventRecord(w[3], st));
   iv.last_page = PageView{true, kp, ke, page_base, (const uint64_t*)S.rec_off.p, arena, page_bytes};
   iv.kp = ke;
-  ticket->arena = ai; ticket->dev = arena; ticket->nbytes = page_bytes; ticket->done_event = (void*)w[3]; S.queue_compression(ai, arena, page_bytes);
+  ticket->arena = ai; ticket->dev = arena; ticket->nbytes = page_bytes; ticket->done_event = (void*)w[3];
+  // the output's index reads the page between the kernels that wrote it and the deflate that overwrites it, and the block offsets behind the deflate
+  const bool indexed = S.index_sink && S.hp.bgzf && page_bytes != 0;
+  if (indexed) S.index_sink->page_records(ai, iv.last_page, (void*)st);
+  S.queue_compression(ai, arena, page_bytes);
+  if (indexed) {
+    uint64_t nblocks = 0;
+    const uint64_t* const boff = S.bgzf->block_offsets(ai, &nblocks);
+    S.index_sink->page_blocks(ai, boff, nblocks, bgzf_block_input(), (void*)st);
+  }
   return true;
 }
 
@@ -6015,6 +6025,7 @@ bool DevicePipeline::next_page(uint64_t arena_bytes, const char** dev_ptr, uint6
 
 const IntervalStats& DevicePipeline::interval_stats() const { return m_->iv.stats; }
 DevicePipeline::PageView DevicePipeline::last_page() const { return m_->iv.last_page; }
+void DevicePipeline::set_page_index_sink(PageIndexSink* sink) { m_->index_sink = sink; }
 FragmentView DevicePipeline::fragment_view() const { return m_->fr; }
 uint64_t DevicePipeline::fragment_generation() const { return m_->fragment_generation; }
 void DevicePipeline::set_page_priority(bool on) { m_->page_priority = on; }

@@ -1,5 +1,5 @@
 // gt_mpi_gather - command line of the reference's query tool:
-//   gt_mpi_gather -j <query.json> [-l <loader.json>] [-r <rank>] [-p <page size>] [-s <segment size>] [-O <fmt>] [--produce-Broad-GVCF | ...]
+//   gt_mpi_gather -j <query.json> [-l <loader.json>] [-r <rank>] [-p <page size>] [-s <segment size>] [-O <fmt>] [--index-on-device] [--produce-Broad-GVCF | ...]
 // Without a mode flag it answers the variants query (gt_get_column_interval + print_variants, tools/src/gt_mpi_gather.cc:102-132, 294): the
 // document of this rank's column partition goes to stdout; the reference's MPI gather of all ranks' variants to rank 0 is not rebuilt.
 // (reference: tools/src/gt_mpi_gather.cc:437-531; scan_and_produce_Broad_GVCF :322-366).  One process per column partition
@@ -22,7 +22,7 @@
 
 using namespace genomicsdb_amd;
 
-enum { ARGS_IDX_PRODUCE_BROAD_GVCF = 1000, ARGS_IDX_PRODUCE_HISTOGRAM, ARGS_IDX_PRINT_CALLS, ARGS_IDX_PRINT_CSV, ARGS_IDX_PRINT_AC, ARGS_IDX_VERSION, ARGS_IDX_UNSUPPORTED };
+enum { ARGS_IDX_PRODUCE_BROAD_GVCF = 1000, ARGS_IDX_PRODUCE_HISTOGRAM, ARGS_IDX_PRINT_CALLS, ARGS_IDX_PRINT_CSV, ARGS_IDX_PRINT_AC, ARGS_IDX_VERSION, ARGS_IDX_UNSUPPORTED, ARGS_IDX_INDEX_ON_DEVICE };
 extern "C" int64_t gdbamd_equi_partition_text(const uint64_t* counts, uint64_t nbins, uint64_t hist_begin, uint64_t bin_size, uint64_t num_parts, char* dst, uint64_t cap);
 
 static int launcher_rank() {
@@ -38,11 +38,11 @@ int main(int argc, char** argv) {
       {"produce-Broad-GVCF", 0, 0, ARGS_IDX_PRODUCE_BROAD_GVCF}, {"version", 0, 0, ARGS_IDX_VERSION},
       {"skip-query-on-root", 0, 0, ARGS_IDX_UNSUPPORTED}, {"produce-interesting-positions", 0, 0, ARGS_IDX_UNSUPPORTED},
       {"produce-histogram", 0, 0, ARGS_IDX_PRODUCE_HISTOGRAM}, {"print-calls", 0, 0, ARGS_IDX_PRINT_CALLS}, {"print-csv", 0, 0, ARGS_IDX_PRINT_CSV},
-      {"print-AC", 0, 0, ARGS_IDX_PRINT_AC}, {0, 0, 0, 0}};
+      {"print-AC", 0, 0, ARGS_IDX_PRINT_AC}, {"index-on-device", 0, 0, ARGS_IDX_INDEX_ON_DEVICE}, {0, 0, 0, 0}};
   std::string json_config, loader_json, output_format;
   size_t page_size = 0, segment_size = 10u * 1024u * 1024u;
   int rank = launcher_rank();
-  bool produce_gvcf = false, produce_histogram = false, print_calls = false;
+  bool produce_gvcf = false, produce_histogram = false, print_calls = false, index_on_device = false;
   int print_mode = 0;
   int c;
   while ((c = getopt_long(argc, argv, "j:l:w:A:p:O:s:r:", long_options, NULL)) >= 0) {
@@ -59,13 +59,14 @@ int main(int argc, char** argv) {
       case ARGS_IDX_PRINT_CALLS: print_calls = true; print_mode = 0; break;
       case ARGS_IDX_PRINT_CSV: print_calls = true; print_mode = 1; break;
       case ARGS_IDX_PRINT_AC: print_calls = true; print_mode = 2; break;
+      case ARGS_IDX_INDEX_ON_DEVICE: index_on_device = true; break;
       case ARGS_IDX_VERSION: std::cout << "genomicsdb_amd (MI355X variant-combine path) for GenomicsDB 0.10.2 query JSON\n"; return 0;
       case ARGS_IDX_UNSUPPORTED: std::cerr << "this build implements the variants query (no mode flag), --produce-Broad-GVCF, --produce-histogram, --print-calls, --print-csv and --print-AC only\n"; return -1;
       default: std::cerr << "Unknown command line argument\n"; return -1;
     }
   }
   if (json_config.empty()) {
-    std::cerr << "Usage: gt_mpi_gather -j <query.json> [-l <loader.json>] [-r rank] [-p page_size] [-O output_format] [--produce-Broad-GVCF | --produce-histogram | --print-calls | --print-csv | --print-AC]\n"
+    std::cerr << "Usage: gt_mpi_gather -j <query.json> [-l <loader.json>] [-r rank] [-p page_size] [-O output_format] [--index-on-device] [--produce-Broad-GVCF | --produce-histogram | --print-calls | --print-csv | --print-AC]\n"
                  "without a mode flag: the variants of the query intervals as JSON on stdout, one process per column partition (the ranks' documents are not gathered to rank 0)\n";
     return -1;
   }
@@ -132,6 +133,12 @@ int main(int argc, char** argv) {
       }
       if (output_format.empty() && q.IsObject() && q.HasMember("vcf_output_format") && q["vcf_output_format"].IsString()) output_format = q["vcf_output_format"].GetString();
     }
+    // --index-on-device: with "index_output_VCF" the .tbi / .csi comes from the stream's pages while they are in device memory, not from re-reading the file
+    if (index_on_device && out_name.empty()) { std::cerr << "gt_mpi_gather: --index-on-device needs an output file (\"vcf_output_filename\"): a stream to stdout has no index next to it\n"; return -1; }
+    if (index_on_device && output_format != "z" && output_format != "b") {
+      std::cerr << "gt_mpi_gather: --index-on-device needs -O z or -O b: output format \"" << output_format << "\" is not BGZF-compressed and has no index\n";
+      return -1;
+    }
     FILE* out = out_name.empty() ? stdout : fopen(out_name.c_str(), "wb");
     if (!out) { std::cerr << "cannot open " << out_name << "\n"; return -1; }
     const size_t capacity = page_size ? page_size : (size_t)64u << 20;
@@ -140,6 +147,8 @@ int main(int argc, char** argv) {
     const auto t0 = std::chrono::steady_clock::now();
     GenomicsDBBCFGenerator gen(loader_json, json_config, "", 0, 0, rank, capacity, segment_size, output_format.c_str(), false, false, true,
                                true);   // (-O z / b: BGZF like the reference's file-writing VCFAdapter, vcf_adapter.cc:340-372)
+    const bool device_index = index_on_device && index_output;
+    if (device_index) gen.enable_output_index();
     std::vector<uint8_t> buf(std::max<size_t>(capacity, 1u << 20));
     size_t total = 0;
     while (!gen.end()) {
@@ -149,7 +158,10 @@ int main(int argc, char** argv) {
       total += n;
     }
     if (out != stdout) fclose(out); else fflush(stdout);
-    if (out != stdout && index_output && (output_format == "z" || output_format == "b")) {   // vcf_adapter.cc:275-295: the index from the finished file
+    if (device_index) {
+      try { gen.write_output_index(out_name + (output_format == "z" ? ".tbi" : ".csi")); }
+      catch (const std::exception& e) { std::cerr << "WARNING: error in creating index for output file " << out_name << ": " << e.what() << "\n"; }
+    } else if (out != stdout && index_output && (output_format == "z" || output_format == "b")) {   // vcf_adapter.cc:275-295: the index from the finished file
       try { if (output_format == "z") build_tbi_index(out_name); else build_csi_index(out_name); }
       catch (const std::exception& e) { std::cerr << "WARNING: error in creating index for output file " << out_name << ": " << e.what() << "\n"; }
     }

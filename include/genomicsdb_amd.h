@@ -88,6 +88,22 @@ typedef struct gdb_mi355_stream_stats {
   double seconds_producing;                      /* host time inside the sweep / sizing / page launches (reader blocked) */
 } gdb_mi355_stream_stats;
 int gdb_mi355_get_stream_stats(void* handle, gdb_mi355_stream_stats* out);
+/* The index of a "z" / "b" stream's bytes as a file - .tbi / .csi -, built ON THE DEVICE from every page while it is in HBM
+ * (kernels/gdb_output_index.h): the file gdbamd_build_output_index writes for the finished file, byte for byte, without re-reading it.
+ * gdb_mi355_enable_index: only for the output formats "z" / "b", and only before the first body page is produced (before the header
+ * has been read to its end).  gdb_mi355_write_index: only once the stream has been read to its end; writes `path` (the caller's
+ * choice: <file>.tbi / <file>.csi) and fills *stats (may be NULL).  0, or -1 with gdb_mi355_last_error() saying which condition
+ * failed; the stream stays usable as it was. */
+typedef struct gdb_mi355_index_stats {
+  int64_t pages, records;                        /* device pages indexed, records in them */
+  int64_t contigs, bins, chunks, linear_windows; /* of the index as written (bins without the meta bin) */
+  int64_t atomics;                               /* atomicMin issued on the window minima */
+  double ms_records, ms_voff, ms_chunks, ms_linear; /* device time per phase, summed over the pages */
+  double s_write;                                /* wall clock: merge of the pages, layout, compression, file write */
+  uint64_t table_bytes;                          /* device memory held by the record tables */
+} gdb_mi355_index_stats;
+int gdb_mi355_enable_index(void* handle);
+int gdb_mi355_write_index(void* handle, const char* path, gdb_mi355_index_stats* stats);
 
 /* ---- (2) engine ------------------------------------------------------------------------------------------ */
 typedef struct gdbamd_interval_stats {
