@@ -18,7 +18,8 @@ class IntervalStats(ctypes.Structure):
                 ("num_text_slots", ctypes.c_int64), ("text_pool_bytes", ctypes.c_int64),
                 ("num_remap_elements", ctypes.c_uint64), ("bytes_compressed", ctypes.c_uint64), ("ms_compress", ctypes.c_float),
                 ("page_kernel", ctypes.c_int32), ("gt_profile_stats", ctypes.c_uint64 * 6),
-                ("huge_records", ctypes.c_int32), ("huge_fallbacks", ctypes.c_int32)]
+                ("huge_records", ctypes.c_int32), ("huge_fallbacks", ctypes.c_int32),
+                ("sorted_median_fields", ctypes.c_int32), ("big_median_records", ctypes.c_int32), ("big_median_unlisted", ctypes.c_int32)]
 
     # names of the reference's GTProfileStats counters (query_variants.h:67-124), in enum order
     GT_STAT_NAMES = ("GT_NUM_CELLS", "GT_NUM_CELLS_IN_LEFT_SWEEP", "GT_NUM_VALID_CELLS_IN_QUERY", "GT_NUM_ATTR_CELLS_ACCESSED",

@@ -332,6 +332,7 @@ static void fill_interval_stats(gdbamd_interval_stats* out, const IntervalStats&
   out->bytes_compressed = s.bytes_compressed; out->ms_compress = s.ms_compress; out->page_kernel = s.page_kernel;
   for (int i = 0; i < GDBAMD_GT_NUM_STATS; ++i) out->gt_profile_stats[i] = s.gt_profile[i];
   out->huge_records = s.huge_records; out->huge_fallbacks = s.huge_fallbacks;
+  out->sorted_median_fields = s.sorted_median_fields; out->big_median_records = s.big_median_records; out->big_median_unlisted = s.big_median_unlisted;
 }
 int gdbamd_engine_run_interval(void* e, int64_t qb, int64_t qe, uint64_t arena_bytes, char* host_out, uint64_t host_cap, uint64_t* host_len,
                                gdbamd_interval_stats* out) {

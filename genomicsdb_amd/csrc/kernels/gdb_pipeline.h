@@ -44,6 +44,9 @@ struct IntervalStats {
   int page_kernel = 0;             // digits S K W C II of the most recent page launch (see include/genomicsdb_amd.h), set at the launch sites; 0: no page yet
   int huge_records = 0;            // records whose call walk the workgroup-per-record site kernel (k_site_huge) was given; 0: not launched
   int huge_fallbacks = 0;          // ... of which it handed back to the serial walk (hash collision, table overflow, several FILTER ids)
+  int sorted_median_fields = 0;    // median fields ordered by the device-wide sort (k_median_keys); 0: that path was not taken
+  int big_median_records = 0;      // records k_big_records listed for the workgroup medians (k_big_medians); 0: not launched
+  int big_median_unlisted = 0;     // ... records that qualified but found the list of kMaxBigRecords full
   // the reference's GTProfileStats counters (query_variants.h:67-124), per interval; see include/genomicsdb_amd.h
   uint64_t gt_profile[6] = {0, 0, 0, 0, 0, 0};
 };

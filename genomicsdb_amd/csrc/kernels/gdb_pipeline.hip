@@ -5503,6 +5503,7 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
         med.slot[fields[s].first] = (int8_t)s;
       }
       med.keys = S.med_keys_sorted.p; med.inc = S.med_idx_sorted.p; med.stride = T; med.enabled = 1;
+      stats.sorted_median_fields = (int)fields.size();
     }
   }
   // records with very many variant calls get their medians from one workgroup each (no host round trip: the list is built
@@ -5635,11 +5636,15 @@ void DevicePipeline::prepare_interval(int64_t qb, int64_t qe) {
   S.excl_scan(S.nslots.p, S.tbase.p, (size_t)CW);
   uint32_t ur_a = 0, ur_b = 0, sl_a = 0, sl_b = 0;
   int32_t ntypes = 0;
-  int32_t huge_counts[4] = {0, 0, 0, 0};      // counters[3]: records k_huge_records listed, counters[6]: the ones k_site_huge handed back (0 when not launched)
+  // counters[2]: records that qualified at k_big_records, counters[3]: records k_huge_records listed, counters[6]: the ones k_site_huge handed back
+  // (each 0 when its kernel was not launched)
+  int32_t path_counts[5] = {0, 0, 0, 0, 0};
   S.read_back_many({{&ur_a, S.ubase.p + (P - 1), 4}, {&ur_b, S.untabled.p + (P - 1), 4}, {&sl_a, S.tbase.p + (CW - 1), 4}, {&sl_b, S.nslots.p + (CW - 1), 4},
-                    {&ntypes, S.counters.p + 1, 4}, {huge_counts, S.counters.p + 3, sizeof(huge_counts)}});
-  stats.huge_records = std::min(huge_counts[0], (int32_t)kMaxHugeRecords);
-  stats.huge_fallbacks = huge_counts[3];
+                    {&ntypes, S.counters.p + 1, 4}, {path_counts, S.counters.p + 2, sizeof(path_counts)}});
+  stats.big_median_records = std::min(path_counts[0], (int32_t)kMaxBigRecords);
+  stats.big_median_unlisted = std::max(path_counts[0] - (int32_t)kMaxBigRecords, 0);
+  stats.huge_records = std::min(path_counts[1], (int32_t)kMaxHugeRecords);
+  stats.huge_fallbacks = path_counts[4];
   const int64_t UR = (int64_t)ur_a + ur_b;
   const uint64_t SL = (uint64_t)sl_a + sl_b;
   if (UR > 0) hipLaunchKernelGGL(k_untabled_records, dim3(blocks_for(P)), dim3(kBlock), 0, st, S.untabled.p, S.ubase.p, P, S.urec.p);

@@ -134,6 +134,12 @@ typedef struct gdbamd_interval_stats {
                                           * record) that one workgroup each did their call walk (k_site_huge); 0 when that kernel was not launched */
   int32_t huge_fallbacks;                /* ... of which the kernel handed back to the one-thread walk: two alleles with one 32-bit hash, a full allele
                                           * table, several different FILTER ids */
+  /* which code took the interval's medians (`median` reducer of INFO fields and QUAL) */
+  int32_t sorted_median_fields;          /* median fields ordered by the device-wide sort (the interval averages more than 16 variant calls per record, or
+                                          * GDBAMD_SORTED_MEDIAN is set); 0: that path was not taken */
+  int32_t big_median_records;            /* records with 49 .. 4096 variant calls whose medians one workgroup each took (k_big_medians): at most 4096 are
+                                          * listed per interval; 0 when the medians were sorted or the interval has no median field */
+  int32_t big_median_unlisted;           /* ... further such records that found the list full: their medians come from the site kernels */
 } gdbamd_interval_stats;
 enum { GDBAMD_GT_NUM_CELLS = 0, GDBAMD_GT_NUM_CELLS_IN_LEFT_SWEEP, GDBAMD_GT_NUM_VALID_CELLS_IN_QUERY, GDBAMD_GT_NUM_ATTR_CELLS_ACCESSED,
        GDBAMD_GT_NUM_PQ_FLUSHES_DUE_TO_OVERLAPPING_CELLS, GDBAMD_GT_NUM_OPERATOR_INVOCATIONS, GDBAMD_GT_NUM_STATS };

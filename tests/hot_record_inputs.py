@@ -12,6 +12,7 @@ Every builder returns (cells, query, facts).  facts["intervals"] is a list of di
   merged_ref            {column: merged REF}
   num_records, heavy    IntervalStats.num_records / num_heavy_incidences the interval must report
   huge_records, huge_fallbacks   the counters of the default mode
+  sorted, big_records, big_listed, big_unlisted   which code takes the medians (median_path_facts)
 A test asserts the facts it states by hand against these before it compares any bytes (check_facts does the part every case shares)."""
 import gzip
 import json
@@ -74,9 +75,9 @@ def hom_index(a, ploidy):
 class Call:
     """one gVCF line of one sample (the sample's row is its place in the list a builder hands to _import)"""
 
-    def __init__(self, pos, ref, alts, nr=True, ploidy=2, pl=True, info=None, hom_pl=None, filt="."):
-        self.pos, self.ref, self.alts, self.nr, self.ploidy, self.pl, self.info, self.hom_pl, self.filt = \
-            pos, ref, list(alts), nr, ploidy, pl, info or {}, hom_pl or {}, filt
+    def __init__(self, pos, ref, alts, nr=True, ploidy=2, pl=True, info=None, hom_pl=None, filt=".", qual="100"):
+        self.pos, self.ref, self.alts, self.nr, self.ploidy, self.pl, self.info, self.hom_pl, self.filt, self.qual = \
+            pos, ref, list(alts), nr, ploidy, pl, info or {}, hom_pl or {}, filt, qual      # qual: the column's text ("." is a missing QUAL)
 
     def is_symbolic(self, a):
         return a == "*" or (a.startswith("<") and a.endswith(">")) or "[" in a or "]" in a
@@ -102,18 +103,31 @@ class Call:
             fmt.append("PL")
             val.append(",".join(map(str, pl)))
         info = ["DP=%d" % sum(ad), "MQ=40.5"] + ["%s=%s" % kv for kv in self.info.items()]
-        return "1\t%d\t.\t%s\t%s\t100\t%s\t%s\t%s\t%s\n" % (self.pos, self.ref, ",".join(alleles), self.filt, ";".join(info), ":".join(fmt), ":".join(val))
+        return "1\t%d\t.\t%s\t%s\t%s\t%s\t%s\t%s\t%s\n" % (self.pos, self.ref, ",".join(alleles), self.qual, self.filt, ";".join(info), ":".join(fmt), ":".join(val))
 
 
-def merge_at(samples, pos):
+def live_index(samples):
+    """{pos: [(row, call) live there, in row order]}: what merge_at finds call by call, for inputs of many columns"""
+    index = {}
+    for row, calls in enumerate(samples):
+        for c in calls:
+            for pos in range(c.pos, (c.end() if c.has_deletion() else c.pos) + 1):
+                index.setdefault(pos, []).append((row, c))
+    return index
+
+
+def merge_at(samples, pos, index=None):
     """(calls live at pos in row order, merged REF, merged ALT list without <NON_REF>, any <NON_REF>) as merge_alt_alleles leaves them:
     the longest REF among the calls that start at pos (the lowest row at equal length); every ALT extended by the part of the merged REF
     its own REF lacks, symbolic ones as they are, a deletion that began earlier as '*'; first appearance in (row, token) order"""
     live = []
-    for row, calls in enumerate(samples):
-        for c in calls:
-            if c.pos == pos or (c.pos < pos <= c.end() and c.has_deletion()):
-                live.append((row, c))
+    if index is not None:
+        live = index.get(pos, [])
+    else:
+        for row, calls in enumerate(samples):
+            for c in calls:
+                if c.pos == pos or (c.pos < pos <= c.end() and c.has_deletion()):
+                    live.append((row, c))
     mref = ""
     for row, c in live:
         if c.pos == pos and len(c.ref) > len(mref):
@@ -139,18 +153,36 @@ def huge_threshold(T, P):
     return 24 if (P > 0 and T // P >= 24 and P <= 8192) else 256
 
 
+SORTED_MEDIAN_THRESHOLD = 16    # kSortedMedianThreshold
+BIG_RECORD = 48                 # kBigRecord
+BIG_CAPACITY = 4096             # kBigCapacity
+MAX_BIG_RECORDS = 4096          # kMaxBigRecords
+
+
+def median_path_facts(calls):
+    """which code takes the medians of an interval whose records have calls = {column: variant calls}: every median field is ordered by one
+    device-wide sort when the interval averages more than 16 calls a record (T > 16 P); otherwise the records with 49 .. 4096 calls are
+    listed for one workgroup each (k_big_records / k_big_medians), the first 4096 of them"""
+    P, T = len(calls), sum(calls.values())
+    is_sorted = T > SORTED_MEDIAN_THRESHOLD * P
+    big = [] if is_sorted else sorted(col for col, n in calls.items() if BIG_RECORD < n <= BIG_CAPACITY)
+    return {"sorted": is_sorted, "big_records": big, "big_listed": min(len(big), MAX_BIG_RECORDS), "big_unlisted": max(len(big) - MAX_BIG_RECORDS, 0)}
+
+
 def interval_facts(samples, begin_pos, end_pos):
     """the facts of the column interval [begin_pos - 1, end_pos - 1], derived from the input lines alone"""
     starts = sorted({c.pos for calls in samples for c in calls if begin_pos <= c.pos <= end_pos} | {begin_pos})
+    index = live_index(samples)
     recs = {}
     for pos in starts:
-        live, mref, merged, any_nr = merge_at(samples, pos)
+        live, mref, merged, any_nr = merge_at(samples, pos, index)
         if live:
             recs[pos] = (live, mref, merged, any_nr)
     P, T = len(recs), sum(len(r[0]) for r in recs.values())
     thr = huge_threshold(T, P)
     hot = {pos: r for pos, r in recs.items() if len(r[0]) > thr}
-    return {"begin": begin_pos - 1, "end": end_pos - 1, "num_records": P, "heavy": T, "threshold": thr,
+    return {**median_path_facts({pos - 1: len(r[0]) for pos, r in recs.items()}),
+            "begin": begin_pos - 1, "end": end_pos - 1, "num_records": P, "heavy": T, "threshold": thr,
             "calls": {pos - 1: len(r[0]) for pos, r in recs.items()},
             "distinct": {pos - 1: len(r[2]) for pos, r in recs.items()},
             "merged_ref": {pos - 1: r[1] for pos, r in recs.items()},
@@ -165,6 +197,7 @@ def check_facts(facts):
     for iv in facts["intervals"]:
         assert iv["num_records"] >= 1 and iv["heavy"] == sum(iv["calls"].values())
         assert 0 <= iv["huge_fallbacks"] <= iv["huge_records"] <= iv["num_records"]
+        assert iv["big_listed"] + iv["big_unlisted"] == len(iv["big_records"]) <= iv["num_records"] and not (iv["sorted"] and iv["big_records"])
 
 
 _head_text = None
@@ -178,10 +211,10 @@ def _head():
     return _head_text
 
 
-def _import(tmp_path, samples, seed, reducers=False, attributes=None, reference=True):
+def _import(tmp_path, samples, seed, reducers=False, attributes=None, reference=True, qual_median=False):
     """samples[row] = [Call, ...] -> (cells, query): one .vcf.gz per sample through the host importer.  reference=False: the query names no
     reference genome (every record of the case has a call that starts at it and brings its REF along; the oracle reads the genome anew on
-    every run, a tenth of a second)"""
+    every run, a tenth of a second).  qual_median: the vid gives QUAL the median reducer and the query asks for QUAL"""
     import genomicsdb_amd
     rnd = random.Random(seed)
     vid = os.path.join(helpers.GOLDEN, "inputs", "vid.json")
@@ -191,6 +224,8 @@ def _import(tmp_path, samples, seed, reducers=False, attributes=None, reference=
         for name, (typ, op) in REDUCER_FIELDS.items():
             v["fields"][name] = {"vcf_field_class": ["INFO"], "type": typ, "VCF_field_combine_operation": op}
             extra += '##INFO=<ID=%s,Number=1,Type=%s,Description="x">\n' % (name, "Integer" if typ == "int" else "Float")
+        if qual_median:
+            v["fields"]["QUAL"] = {"type": "float", "VCF_field_combine_operation": "median"}
         vid = str(tmp_path / "vid.json")
         with open(vid, "w") as f:
             json.dump(v, f)
@@ -210,7 +245,7 @@ def _import(tmp_path, samples, seed, reducers=False, attributes=None, reference=
     assert ncells == ncalls
     attrs = attributes or ["REF", "ALT", "DP", "MQ", "GT", "AD", "GQ", "PL", "DP_FORMAT", "MIN_DP"]
     if reducers:
-        attrs = attrs + list(REDUCER_FIELDS)
+        attrs = attrs + list(REDUCER_FIELDS) + (["QUAL"] if qual_median else [])
     q = {"vid_mapping_file": vid, "callset_mapping_file": str(cs),
          "vcf_header_filename": os.path.join(helpers.GOLDEN, "inputs", "template_vcf_header.vcf"),
          "reference_genome": os.path.join(helpers.GOLDEN, "inputs", "chr1_10MB.fasta.gz"),
@@ -501,6 +536,229 @@ def reducers_large(tmp_path, n):
     return reducer_columns(tmp_path, [col], seed=n)
 
 
+# ---- reducer columns among other records: which code takes a median ------------------------------------------------------------------------
+# The median of a record comes from one of four pieces of code, chosen from the counts of the INTERVAL (median_path_facts; the workgroup
+# site kernel k_site_huge and the per-thread scan of reduce_scalar are the other two).  A single-column interval with 25 and more calls is
+# always sorted; these inputs put the hot columns among `pad` columns of one call each, so that the average can be set at will.
+MEDIAN_FIELDS = ("IMED", "FMED", "QUAL")      # three median slots: two INFO fields (spanning deletions do not count) and QUAL (they do)
+
+
+def f32(x):
+    """x rounded to a float: what a cell stores"""
+    import numpy as np
+    return float(np.float32(x))
+
+
+def reducer_interval(tmp_path, columns, pad, pad_first=False, seed=47):
+    """columns as reducer_columns takes them; besides the fields of REDUCER_FIELDS a column may carry "QUAL": [value or None per call] (100
+    without it) and "spanning": the rows whose call is a deletion that begins one column earlier (REF TG, ALT T: it ends at the hot column).
+    The hot columns (ten apart) and the pad columns (two apart, SNVs without reducer fields, QUAL 100) are queried as ONE interval that
+    begins at HOT.  pad: a number of columns with one call each, in row j modulo the rows of the hot columns, or a list of calls per
+    column, in rows 0 .. calls - 1.  pad_first: the pad columns come first, the last hot column is the last record"""
+    counts = [len(next(v for k, v in col.items() if k != "spanning")) for col in columns]
+    nrows = max(counts)
+    pads = [(j % nrows,) for j in range(pad)] if isinstance(pad, int) else [tuple(range(c)) for c in pad]
+    nrows = max([nrows] + [len(rows) for rows in pads])
+    hot0 = HOT + 2 * len(pads) + 10 if pad_first else HOT
+    pad0 = HOT if pad_first else HOT + 10 * len(columns)
+    positions = [hot0 + 10 * i for i in range(len(columns))]
+    samples = [[] for _ in range(nrows)]
+    for pos, col, n in zip(positions, columns, counts):
+        spanning = col.get("spanning", ())
+        assert all(len(v) == n for k, v in col.items() if k != "spanning") and all(0 <= r < n for r in spanning)
+        for row in range(n):
+            info = {f: _fmt(col[f][row]) for f in REDUCER_FIELDS if f in col and col[f][row] is not None}
+            qual = "100" if "QUAL" not in col else "." if col["QUAL"][row] is None else _fmt(col["QUAL"][row])
+            if row in spanning:
+                samples[row].append(Call(pos - 1, "TG", ["T"], pl=False, info=info, qual=qual))
+            else:
+                samples[row].append(Call(pos, "G", ["T"], pl=False, info=info, qual=qual))
+    for j, rows in enumerate(pads):
+        for row in rows:
+            samples[row].append(Call(pad0 + 2 * j, "A", ["C"], pl=False))
+    cells, q = _import(tmp_path, samples, seed, reducers=True, attributes=["REF", "ALT", "GT", "DP"], reference=False, qual_median=True)
+    last = max(positions[-1], pad0 + 2 * (len(pads) - 1))
+    return cells, q, {"intervals": [interval_facts(samples, HOT, last)], "columns": columns, "positions": positions}
+
+
+def valid_values(col, field):
+    """the values of one column that count for a field's reducer: not missing, and for an INFO field not on a spanning deletion"""
+    if field not in col:
+        return [100.0] * len(col["IMED"]) if field == "QUAL" else []
+    skip = () if field == "QUAL" else col.get("spanning", ())
+    return [v for row, v in enumerate(col[field]) if v is not None and row not in skip]
+
+
+def median_by_hand(values):
+    """the reference's median: std::nth_element at size / 2"""
+    return sorted(values)[len(values) // 2] if values else None
+
+
+def _mcol(rnd, n, **over):
+    """a column of n calls with ordinary values on every reducer field and on QUAL"""
+    ints = lambda: [rnd.randint(-900, 300) for _ in range(n)]                        # noqa: E731
+    floats = lambda: [rnd.randint(-4000, 2000) / 8.0 for _ in range(n)]              # noqa: E731
+    c = {"ISUM": ints(), "IMEAN": ints(), "IMED": ints(), "FSUM": floats(), "FMEAN": floats(), "FMED": floats(),
+         "QUAL": [rnd.randint(1, 8000) / 8.0 for _ in range(n)]}
+    c.update(over)
+    return c
+
+
+def _shuffled(rnd, values):
+    values = list(values)
+    rnd.shuffle(values)
+    return values
+
+
+def _among_missing(rnd, n, values):
+    """values on random rows of n calls, the other rows missing"""
+    out = [None] * n
+    for row, v in zip(rnd.sample(range(n), len(values)), values):
+        out[row] = v
+    return out
+
+
+def median_48_49(tmp_path):
+    """48 calls are no big record, 49 are; five pad columns: T = 102 <= 16 x 7"""
+    rnd = random.Random(51)
+    return reducer_interval(tmp_path, [_mcol(rnd, 48), _mcol(rnd, 49)], 5)
+
+
+def median_average_16(tmp_path, one_more):
+    """P = 4 records with 49 + 13 + 1 + 1 = 64 = 16 P calls: the 49 are a big record; one call more on a pad column and the medians are sorted"""
+    rnd = random.Random(52)
+    return reducer_interval(tmp_path, [_mcol(rnd, 49), _mcol(rnd, 13)], [1, 2 if one_more else 1])
+
+
+def median_sorted_single(tmp_path):
+    """P = 1 record with 20 calls: sorted (the key holds no record bits) and no record for k_site_huge"""
+    rnd = random.Random(54)
+    return reducer_interval(tmp_path, [_mcol(rnd, 20, IMED=_among_missing(rnd, 20, [rnd.randint(-900, 300) for _ in range(18)]))], 0)
+
+
+def median_sorted_last_of_4(tmp_path):
+    """P = 4, a power of two, and the 70 calls are the LAST record (k = 3: both record bits of the sort key set); T = 73 > 64, T / P < 24"""
+    rnd = random.Random(55)
+    return reducer_interval(tmp_path, [_mcol(rnd, 70, FMED=_among_missing(rnd, 70, [rnd.randint(-4000, 2000) / 8.0 for _ in range(64)]))], 3, pad_first=True)
+
+
+MEDIAN_VALUE_COLUMN_NAMES = ["odd49", "even50", "even50_among_53", "all_equal", "one_valid", "none_valid", "extremes", "zeros49", "zeros50", "zeros51",
+                             "both_zero_signs_beside_the_median", "zero_median_plus_only", "zero_median_minus_only"]
+
+
+def median_values(tmp_path):
+    """thirteen big records of 49 - 55 calls among 30 pad columns (T = 683 <= 16 x 43): see MEDIAN_VALUE_COLUMN_NAMES.  extremes: ints from
+    -2147483646, the smallest valid one (INT32_MIN is "missing", INT32_MIN + 1 "vector end"), to 2147483647; floats around -3e38 and
+    denormals of both signs, the median a denormal"""
+    rnd = random.Random(53)
+    ints = lambda n: [rnd.randint(-900, 300) for _ in range(n)]                      # noqa: E731
+    floats = lambda n: [rnd.randint(-4000, 2000) / 8.0 for _ in range(n)]            # noqa: E731
+    quals = lambda n: [rnd.randint(1, 8000) / 8.0 for _ in range(n)]                 # noqa: E731
+    lone = lambda v: [v if row == 17 else None for row in range(55)]                 # noqa: E731
+    around = lambda zero: _shuffled(rnd, [-(1.5 + i) for i in range(10)] + [0.25 + i for i in range(10)] + [zero] * 29)     # noqa: E731
+    beside = lambda: _shuffled(rnd, [-0.0, 0.0] + [1.0 + i / 8.0 for i in range(47)])                                     # noqa: E731
+    columns = [_mcol(rnd, 49), _mcol(rnd, 50),
+               _mcol(rnd, 53, IMED=_among_missing(rnd, 53, ints(50)), FMED=_among_missing(rnd, 53, floats(50)), QUAL=_among_missing(rnd, 53, quals(50))),
+               _mcol(rnd, 49, IMED=[-3] * 49, FMED=[-2.5] * 49, QUAL=[7.25] * 49),
+               _mcol(rnd, 55, IMED=lone(-41), FMED=lone(-2.75), QUAL=lone(3.5)),
+               _mcol(rnd, 49, IMED=[None] * 49, FMED=[None] * 49, QUAL=[None] * 49),
+               _mcol(rnd, 51, IMED=_shuffled(rnd, [-2147483646 + i for i in range(26)] + [2147483647 - i for i in range(25)]),
+                     FMED=_shuffled(rnd, [f32(-3.0e38 + i * 1e37) for i in range(20)] + [f32(-(i + 1) * 1e-41) for i in range(10)] + [f32((i + 1) * 1e-42) for i in range(21)]),
+                     QUAL=_shuffled(rnd, [f32((i + 1) * 1e-41) for i in range(30)] + [f32(3.0e38 - i * 1e37) for i in range(21)]))]
+    for n in (49, 50, 51):
+        columns.append(_mcol(rnd, n, FMED=_tied_zero_column(rnd, n), QUAL=_tied_zero_column(rnd, n)))
+    columns += [_mcol(rnd, 49, FMED=beside(), QUAL=beside()), _mcol(rnd, 49, FMED=around(0.0), QUAL=around(0.0)), _mcol(rnd, 49, FMED=around(-0.0), QUAL=around(-0.0))]
+    return reducer_interval(tmp_path, columns, 30)
+
+
+def median_spanning(tmp_path):
+    """two big records of which rows 0 - 11 are deletions that begin one column earlier.  Their INFO and QUAL values lie below all others:
+    counting them would move an INFO median down (they must not count), leaving them out would move the QUAL median up (they must
+    count).  The first record keeps 48 valid INFO values of 60 calls - it is listed all the same, a record is big by its calls - the second
+    50 of 62; the deletions of the second begin inside the interval and are a record of 12 calls themselves"""
+    rnd = random.Random(59)
+    columns = []
+    for n in (60, 62):
+        k = n - 12
+        columns.append(_mcol(rnd, n, spanning=set(range(12)),
+                             IMED=[-1000 - r for r in range(12)] + _shuffled(rnd, range(1, k + 1)),
+                             FMED=[-500.5 - r for r in range(12)] + _shuffled(rnd, [i + 0.5 for i in range(1, k + 1)]),
+                             QUAL=[1.5 + r for r in range(12)] + _shuffled(rnd, [100.0 + i for i in range(1, k + 1)])))
+    return reducer_interval(tmp_path, columns, 6)
+
+
+GRID_STRIDE_VALID = (49, 2, 1, 0)
+
+
+def median_grid_stride(tmp_path):
+    """70 big records for the 64 workgroups of k_big_medians: six workgroups take a second record.  Consecutive records have 49, 2, 1 and 0
+    valid values (what a workgroup left in LDS for the record before must not count) and no two records one median"""
+    rnd = random.Random(61)
+    columns = []
+    for i in range(70):
+        v = GRID_STRIDE_VALID[i % 4]
+        columns.append(_mcol(rnd, 49, IMED=_among_missing(rnd, 49, [100 * i + k for k in range(v)]),
+                             FMED=_among_missing(rnd, 49, [100 * i + k + 0.5 for k in range(v)]),
+                             QUAL=_among_missing(rnd, 49, [10000 + 100 * i + k + 0.25 for k in range(v)])))
+    return reducer_interval(tmp_path, columns, 155)
+
+
+def median_big_and_huge(tmp_path, tied):
+    """300 calls among 19 pad columns (T = 319 <= 16 x 20, so only more than 256 calls make a record of k_site_huge): big and huge at once,
+    the big table is asked first.  tied: zeros of both signs at the middle - the big table says 2, the workgroup site kernel says 2, and
+    the site thread runs the reference's selection"""
+    rnd = random.Random(67)
+    over = dict(FMED=_tied_zero_column(rnd, 300), QUAL=_tied_zero_column(rnd, 300)) if tied else {}
+    return reducer_interval(tmp_path, [_mcol(rnd, 300, **over)], 19)
+
+
+def median_capacity(tmp_path):
+    """4096 calls fill the LDS of k_big_medians, 4097 are too many: that record's medians come from k_site_huge, and without it from the
+    per-thread scan.  545 pad columns: T = 8738 <= 16 x 547"""
+    rnd = random.Random(71)
+    columns = [_mcol(rnd, n, IMED=[rnd.randint(-900, 300) if i % 7 else None for i in range(n)], FMED=_tied_zero_column(rnd, n)) for n in (4096, 4097)]
+    return reducer_interval(tmp_path, columns, [1] * 545)
+
+
+def median_list_overflow(tmp_path):
+    """4100 big records of 49 calls and 9020 pad columns (T = 209920 = 16 P): the list of k_big_records holds 4096, four records find it
+    full - which four depends on the order of the atomics, so no two records have one median"""
+    rnd = random.Random(73)
+    columns = [{"IMED": _shuffled(rnd, [64 * i + k for k in range(49)]), "FMED": _shuffled(rnd, [64 * i + k + 0.5 for k in range(49)]),
+                "QUAL": _shuffled(rnd, [10.25 + 64 * i + k for k in range(49)]), "ISUM": [i % 1000] * 49, "FMEAN": [0.5 * (i % 100)] * 49}
+               for i in range(4100)]
+    return reducer_interval(tmp_path, columns, 9020)
+
+
+def _paths(calls, num_records, is_sorted, big, unlisted=0, huge_records=0):
+    return [dict(calls=calls, num_records=num_records, sorted=is_sorted, big_listed=big, big_unlisted=unlisted, huge_records=huge_records, huge_fallbacks=0)]
+
+
+# name -> (builder, the prediction of the interval): calls T, records P, sorted (T > 16 P), big records listed / unlisted, records of k_site_huge
+MEDIAN_CASES = {
+    "median_48_49": (median_48_49, _paths(48 + 49 + 5, 7, False, 1)),
+    "median_average_16": (lambda t: median_average_16(t, False), _paths(64, 4, False, 1)),
+    "median_average_16_and_one_call": (lambda t: median_average_16(t, True), _paths(65, 4, True, 0)),
+    "median_sorted_single_record": (median_sorted_single, _paths(20, 1, True, 0)),
+    "median_sorted_last_of_4_records": (median_sorted_last_of_4, _paths(73, 4, True, 0)),
+    "median_values": (median_values, _paths(653 + 30, 43, False, 13)),
+    "median_spanning": (median_spanning, _paths(60 + 12 + 62 + 6, 9, False, 2)),
+    "median_grid_stride": (median_grid_stride, _paths(70 * 49 + 155, 225, False, 70)),
+    "median_big_and_huge": (lambda t: median_big_and_huge(t, False), _paths(319, 20, False, 1, huge_records=1)),
+    "median_big_and_huge_tied_zeros": (lambda t: median_big_and_huge(t, True), _paths(319, 20, False, 1, huge_records=1)),
+    "median_capacity": (median_capacity, _paths(4096 + 4097 + 545, 547, False, 1, huge_records=2)),
+    "median_list_overflow": (median_list_overflow, _paths(4100 * 49 + 9020, 13120, False, 4096, unlisted=4)),
+}
+MEDIAN_MODES = ("default", "no_huge", "sorted")       # nothing set, GDBAMD_NO_HUGE_SITES=1, GDBAMD_SORTED_MEDIAN=1
+
+
+def median_counters(iv, mode):
+    """(sorted_median_fields, big_median_records, big_median_unlisted, huge_records, huge_fallbacks) an interval of MEDIAN_CASES must report"""
+    is_sorted = iv["sorted"] or mode == "sorted"
+    huge = (0, 0) if mode == "no_huge" else (iv["huge_records"], iv["huge_fallbacks"])
+    return ((len(MEDIAN_FIELDS), 0, 0) if is_sorted else (0, iv["big_listed"], iv["big_unlisted"])) + huge
+
+
 # ---- the cases both test files run: name -> (builder, what the case predicts for its intervals, in order) ---------------------------------
 def _one(calls, huge_records, huge_fallbacks, **more):
     return [dict(calls=calls, huge_records=huge_records, huge_fallbacks=huge_fallbacks, **more)]
@@ -536,9 +794,11 @@ TOO_MANY = {"cap_127_alts": (lambda t: distinct_alts(t, 130, MAX_MERGED_ALT + 1)
 def check_case(name, facts):
     """the case's stated predictions against the facts derived from its input lines; returns the intervals"""
     check_facts(facts)
-    predicted = CASES[name][1]
+    predicted = (CASES.get(name) or MEDIAN_CASES[name])[1]
     assert len(predicted) == len(facts["intervals"]), name
     for want, iv in zip(predicted, facts["intervals"]):
+        if "sorted" in want:
+            assert (iv["sorted"], iv["big_listed"], iv["big_unlisted"]) == (want["sorted"], want["big_listed"], want["big_unlisted"]), (name, iv["sorted"], iv["big_records"])
         assert iv["heavy"] == want["calls"], (name, iv["heavy"])
         assert iv["num_records"] == want.get("num_records", 1), (name, iv["num_records"])
         assert iv["huge_records"] == want["huge_records"] and iv["huge_fallbacks"] == want["huge_fallbacks"], (name, iv)

@@ -316,6 +316,7 @@ def test_sorted_median_path_gives_the_same_bytes(gdb, tmp_path, monkeypatch):
     want, nrec, _ = helpers.oracle_run_synth(q, cells, synth.SEED, with_header=False)
     got, st = eng.run_interval(B, B + L - 1, arena_bytes=4 << 20)
     assert st.num_records == nrec and got == want
+    assert st.sorted_median_fields > 0 and st.big_median_records == 0      # the sort ran (tests/test_gpu_median_paths.py: every path at its thresholds)
     eng.close()
 
 
@@ -428,7 +429,10 @@ def test_c3_width_10000_samples_matches_oracle(gdb, tmp_path, monkeypatch):
     """BASELINE.json configs[2] at its full sample count (10 000 rows: 157 wavefront-wide sample chunks per record, records of
     ~0.9 MB) on a window the oracle finishes in seconds; pages smaller than some records.  With this many calls per record
     the rank-sum medians land on zeros of both signs: which one is printed ("-0" / "0") follows the reference's
-    std::nth_element, through the workgroup medians and through the sorted medians alike."""
+    std::nth_element.  Which code takes the medians of the first run follows from the window's counts and is asserted, not assumed: the
+    device-wide sort when the window averages more than 16 variant calls per record, else one workgroup per record with 49 .. 4096 calls
+    (k_big_medians) and the site kernels for the rest; the second run forces the sort.  (tests/test_gpu_median_paths.py holds each of these
+    paths to the oracle at its thresholds.)"""
     from genomicsdb_amd import synth
     N, B, L = 10_000, 10_000_000, 40
     eng, q, cells = _c2_engine(gdb, tmp_path, N, B, L)
@@ -437,9 +441,14 @@ def test_c3_width_10000_samples_matches_oracle(gdb, tmp_path, monkeypatch):
     got, st = eng.run_interval(B, B + L - 1, arena_bytes=4 << 20)
     assert st.num_records == nrec and st.pages > 5
     assert got == want
+    print("first run: calls", st.num_heavy_incidences, "records", st.num_records, "sorted_median_fields", st.sorted_median_fields,
+          "big_median_records", st.big_median_records, "big_median_unlisted", st.big_median_unlisted, "huge_records", st.huge_records)
+    assert (st.sorted_median_fields > 0) == (st.num_heavy_incidences > 16 * st.num_records)
+    assert st.sorted_median_fields == 0 or st.big_median_records == 0
     monkeypatch.setenv("GDBAMD_SORTED_MEDIAN", "1")
     got, st = eng.run_interval(B, B + L - 1, arena_bytes=64 << 20)
     assert got == want
+    assert st.sorted_median_fields > 0 and st.big_median_records == 0
     eng.close()
 
 

@@ -16,16 +16,19 @@ def test_struct_mirror_has_the_counters_and_their_names():
     assert list(st.gt_profile()) == ["GT_NUM_CELLS", "GT_NUM_CELLS_IN_LEFT_SWEEP", "GT_NUM_VALID_CELLS_IN_QUERY", "GT_NUM_ATTR_CELLS_ACCESSED",
                                      "GT_NUM_PQ_FLUSHES_DUE_TO_OVERLAPPING_CELLS", "GT_NUM_OPERATOR_INVOCATIONS"]
     # the C header declares the same number of counters in the same place: behind them only the two counters of the
-    # workgroup-per-record site kernel, which end the struct
+    # workgroup-per-record site kernel and the three that say which code took the medians, which end the struct
     import re
     hdr = open(helpers.os.path.join(helpers.ROOT, "include", "genomicsdb_amd.h")).read()
     body = hdr[hdr.index("typedef struct gdbamd_interval_stats {"):hdr.index("} gdbamd_interval_stats;")]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     tail = body[body.index("uint64_t gt_profile_stats[6];"):].split()
-    assert tail == ["uint64_t", "gt_profile_stats[6];", "int32_t", "huge_records;", "int32_t", "huge_fallbacks;"]
-    assert [f[0] for f in _lib.IntervalStats._fields_][-3:] == ["gt_profile_stats", "huge_records", "huge_fallbacks"]
-    assert [f[1] for f in _lib.IntervalStats._fields_][-2:] == [ctypes.c_int32, ctypes.c_int32]
+    assert tail == ["uint64_t", "gt_profile_stats[6];", "int32_t", "huge_records;", "int32_t", "huge_fallbacks;",
+                    "int32_t", "sorted_median_fields;", "int32_t", "big_median_records;", "int32_t", "big_median_unlisted;"]
+    assert [f[0] for f in _lib.IntervalStats._fields_][-6:] == ["gt_profile_stats", "huge_records", "huge_fallbacks", "sorted_median_fields",
+                                                                "big_median_records", "big_median_unlisted"]
+    assert [f[1] for f in _lib.IntervalStats._fields_][-5:] == [ctypes.c_int32] * 5
     assert ctypes.sizeof(_lib.IntervalStats) % 8 == 0
+    assert _lib.IntervalStats.big_median_unlisted.offset == _lib.IntervalStats.gt_profile_stats.offset + 6 * 8 + 4 * 4
 
 
 def _case(name):
